@@ -12,6 +12,12 @@ which is launched in chunks of --iters-per-launch iterations (default 50).
     python bench.py [--gpus N --steps K --warmup W]     (N > 1: spawns N rank processes)
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
 
+Such a plain run sets up, warms up, times the K steps and prints the result
+line.  --full adds what the headline does not need: the ESS / split R-hat
+diagnostics of the timed draws, the converged-ESS run and the CPU baselines.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy
+(dump_outputs), so that two builds can be compared output for output.
+
 Warmup W = untimed warmup iterations of the sampler (the reference's step-size
 rule, Q4), preceded by --clock-warm-ms of untimed device work (default
 --clock-warm-kind same: the sampler kernel on the measured chain set's own
@@ -66,6 +72,17 @@ def parse():
                     help="initial step size (default: the reference warmup rule's converged "
                          "value on the Large model after W = 500, profiles/r1/v9_bench.json)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the ESS / R-hat "
+                         "diagnostics of the timed draws, the converged-ESS run and the CPU "
+                         "baselines (each still switched off by its own --no-* option); "
+                         "without it a run sets up, warms up, times --steps steps and prints "
+                         "the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned "
+                         "(its draw of every chain and the per-chain scalars) as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: a fixed seeded sample of a "
+                         "larger array); the inputs depend only on the arguments")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
                     help="budget of the CPU-oracle baseline sample (rank 0, N=1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -432,6 +449,43 @@ def check(chains, where):
         sys.exit(3)
 
 
+DUMP_BYTES = 64 * 1000 * 1000
+
+
+def last_step_outputs(samples, K, sc, fields):
+    """What the last timed step handed back: its draw of every chain
+    (`samples[:, K - 1, :]`, f32) and the per-chain scalars `fields` of the
+    chain state after it (f64)."""
+    import numpy as np
+
+    out = {}
+    if K >= 1:
+        out["samples_last_step"] = samples[:, K - 1, :].float().cpu().numpy()
+    for f in fields:
+        out[f] = np.asarray(sc[f], np.float64)
+    return out
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: every array of `arrays` as path/<name>.npy (rank r > 0:
+    <name>_rank<r>.npy), float32 or float64.  An array above its share of the
+    64 MB (split evenly over the arrays and ranks) is cut to a fixed, seeded
+    sample of its elements, the same from run to run."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays) * world)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            n = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def clock_warm(ms, dev, scratch=None):
     """Keep the device busy for `ms` milliseconds with work unrelated to the
     measured chains (the GPU raises its clock under sustained load).
@@ -603,7 +657,11 @@ def main_nuts(args):
     # ESS/s of the timed draws (the metric's second half; every chain's
     # draws — a NUTS step always returns a state of its trajectory — with the
     # same R-hat gate as the HMC line; collective under torch.distributed)
-    ess = ess_block(samples, np.ones(C, np.int64), K, elapsed)
+    ess = ess_block(samples, np.ones(C, np.int64), K, elapsed) if args.full else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs,
+                     last_step_outputs(samples, K, sc, ("logp", "step_size", "n_grad")),
+                     rank, world)
     if rank == 0:
         value = leaves_all / elapsed
         # per launch: the timed leaves spread over the launches by their time
@@ -648,11 +706,12 @@ def main_nuts(args):
                               "step_size_median": float(np.median(sc["step_size"]))},
             "accept_stat_mean": float(np.mean(sc["alpha_sum"]) / max(Wm + K, 1)),
             "step_size": float(np.mean(sc["step_size"])),
-            "clock_warm_ms": args.clock_warm_ms,
-            "ess_per_sec": ess.pop("ess_per_sec"),
-            "ess_timed": ess,
+            "clock_warm_ms": args.clock_warm_ms, "full": args.full,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if ess is not None:
+            out["ess_per_sec"] = ess.pop("ess_per_sec")
+            out["ess_timed"] = ess
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = nuts_cpu_baseline(min(args.cpu_seconds, 15.0), args)
             cb["gpu_over_cpu"] = value / cb["value"]
             out["cpu_baseline"] = cb
@@ -746,6 +805,9 @@ def main_mh(args):
     iters_per_launch = min(B, K)
     elapsed = max_over_ranks(elapsed, device=dev)
     total = sum_over_ranks(float(C * K), device=dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs,
+                     last_step_outputs(samples, K, sc, ("logp", "n_accept")), rank, world)
     if rank == 0:
         value = total / elapsed
         # F = 3N + 10D flops per chain-iteration: the swept term's sum of
@@ -774,9 +836,9 @@ def main_mh(args):
                          "kernel": kern, "launch_ms": launch_ms,
                          "iters_per_launch": iters_per_launch, "flops_per_iteration": flops},
             "accept_rate": float(np.mean(sc["n_accept"] / np.maximum(sc["n_total"], 1))),
-            "clock_warm_ms": args.clock_warm_ms,
+            "clock_warm_ms": args.clock_warm_ms, "full": args.full,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = mh_cpu_baseline(min(args.cpu_seconds, 15.0), args, scale)
             cb["gpu_over_cpu"] = value / cb["value"]
             out["cpu_baseline"] = cb
@@ -978,19 +1040,23 @@ def main():
     frozen = int(np.sum(sc["n_accept"] == 0)) if K else 0     # chains that never moved
     frozen = int(max_over_ranks(float(frozen), device=dev))
     eps = float(np.mean(sc["step_size"]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs,
+                     last_step_outputs(samples, K, sc, ("logp", "step_size", "n_accept")),
+                     rank, world)
 
-    # ---- diagnostics on the device (not timed) ----------------------------------
+    # ---- diagnostics on the device (--full; not timed) --------------------------
     # ESS per (chain, element) with the reference rule and split R-hat over the
     # timed draws of the chains that moved (ess_block says when it is null)
     ess = None
     diag_ms = None
     # (every rank takes part: the moment blocks are all-reduced over RCCL)
-    if not args.no_ess and K >= 1:
+    if args.full and not args.no_ess and K >= 1:
         td = time.perf_counter()
         ess = ess_block(samples, sc["n_accept"], K, elapsed)
         diag_ms = (time.perf_counter() - td) * 1e3
     ess_conv = None
-    if not args.no_ess and args.ess_draws > 0:
+    if args.full and not args.no_ess and args.ess_draws > 0:
         ess_conv = converged_ess(prog, C, prog.layout.flatten(init), dev, L, args,
                                  chain_offset=chain_offset, world=world)
     gather_ms = None
@@ -1060,6 +1126,7 @@ def main():
         }
         out["clock_warm_ms"] = args.clock_warm_ms
         out["clock_warm_kind"] = args.clock_warm_kind
+        out["full"] = args.full
         if gather_ms is not None:
             out["gather_ms"] = gather_ms
         out["frozen_chains"] = frozen
@@ -1069,7 +1136,7 @@ def main():
             out["diagnostics_ms"] = diag_ms
         if ess_conv is not None:
             out["ess_converged"] = ess_conv
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             nproc = args.cpu_procs if args.cpu_procs >= 0 else min(15, os.cpu_count() or 1)
             out["cpu_baseline"] = cpu_baseline(G, N, L, max(eps, 1e-4), args.cpu_seconds, nproc,
                                                value)

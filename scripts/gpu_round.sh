@@ -65,12 +65,12 @@ print('$n', round(d['value'] / 1e6, 3), 'M', d['unit'], 'frac', round(r.get('fra
 }
 
 bench_lines() {
-  bench default || return 1
-  bench driver --steps 20 --warmup 5 || return 1
-  bench small --shape small --no-cpu-baseline || return 1
-  bench medium --shape medium --no-cpu-baseline || return 1
-  bench nuts --workload nuts || return 1
-  bench nuts_large --workload nuts --nuts-model hier --shape large --chains 256 --steps 20 --warmup 20 || return 1
+  bench default --full || return 1
+  bench driver --full --steps 20 --warmup 5 || return 1
+  bench small --full --shape small --no-cpu-baseline || return 1
+  bench medium --full --shape medium --no-cpu-baseline || return 1
+  bench nuts --full --workload nuts || return 1
+  bench nuts_large --full --workload nuts --nuts-model hier --shape large --chains 256 --steps 20 --warmup 20 || return 1
 }
 
 prof() {  # name, bench args (one string), rocprof args...

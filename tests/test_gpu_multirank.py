@@ -102,7 +102,7 @@ def test_bench_ranks_gloo(gpu, world, workload):
            f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "20", "--warmup", "5",
-           "--chains", "64", "--no-cpu-baseline", "--clock-warm-ms", "0"]
+           "--chains", "64", "--full", "--no-cpu-baseline", "--clock-warm-ms", "0"]
     cmd += ["--workload", "nuts"] if workload == "nuts" else [
         "--shape", "small", "--gather", "--ess-draws", "400", "--ess-warmup", "100"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=170, env=env, cwd=ROOT)
@@ -130,7 +130,7 @@ def _bench_line(world, chains, extra):
            f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--chains", str(chains),
-           "--no-cpu-baseline", "--clock-warm-ms", "0"] + extra
+           "--full", "--no-cpu-baseline", "--clock-warm-ms", "0"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=170, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -180,7 +180,8 @@ def test_bench_spawns_ranks_itself(gpu):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-           "--warmup", "5", "--chains", "64", "--no-cpu-baseline", "--clock-warm-ms", "0",
+           "--warmup", "5", "--chains", "64", "--full", "--no-cpu-baseline",
+           "--clock-warm-ms", "0",
            "--ess-draws", "200", "--ess-warmup", "50"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=170, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
