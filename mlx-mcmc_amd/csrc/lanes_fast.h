@@ -43,7 +43,11 @@
 //     leapfrog step needs the gradient alone, and the Hamiltonian of the
 //     proposal (hmc.py:139-153) reads log p at the end of the trajectory, so
 //     the intermediate steps' log-p items (their terms' log / normaliser
-//     work, the records' lp pairs and their polls) were never used.
+//     work, the records' lp pairs and their polls) were never used;
+//   * the intermediate steps run two per loop trip (record-line parity 0 then
+//     1, fixed publish / poll addresses, no copies of the carried state at
+//     the latch), and the launch constants of the common layout are compiled
+//     in (SPEC).
 // Results equal k_hmc_lr's up to fp32 summation order; runs are
 // bit-reproducible and independent of how chains are split over launches.
 #pragma once
@@ -65,6 +69,9 @@ constexpr int lf_slot_sws(int F) { return (void)F, 0; }
 constexpr int lf_slot_dm(int F) { return (F & LF_SWS) ? 1 : 0; }
 constexpr int lf_slot_ds(int F) { return lf_slot_dm(F) + ((F & LF_DM) ? 1 : 0); }
 constexpr int lf_nroles(int F) { return lf_slot_ds(F) + ((F & LF_DS) ? 1 : 0); }
+// launch constants fixed at compile time (SPEC bits; run_lanes.h resolves them)
+constexpr int LFS_REP1 = 1;  // LrCtx::rep == 1: no replicated private parameter
+constexpr int LFS_NOXF = 2;  // LrCtx::has_xf == 0: no transformed shared parameter
 
 // pair P -> the row (16-lane group) that holds its total after the
 // reduce-scatter / the slice sums: rows hold values 4n + {0, 2, 1, 3}
@@ -90,32 +97,44 @@ MC_DEV f2 vpin(f2 x) {
 }
 MC_DEV f2 bc2(float x) { return (f2){x, x}; }
 
+// dpp_row (eval.h) without a seed register: every lane of a row has a source
+// lane under these row controls, so the `old` operand is never read; leaving
+// it unspecified spares the zero the other form materialises where the move
+// is not folded into its add.
+template <int CTRL>
+MC_DEV float lf_dpp(float x) {
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), CTRL, 0xF, 0xF, true));
+}
+
 // Reduce-scatter of 8 per-lane values over the wave: returns two registers;
 // row r of register n holds (in all 16 lanes) the wave total of value
 // 4n + {0, 2, 1, 3}[r].  A fixed tree: the same bits in every wave / slice.
-// Z01: v[0] and v[1] are zero in every lane (their totals are +0).
+// Z01: values 0 and 1 carry nothing (an intermediate step has no log-p pair):
+// v[0] and v[1] are not read, and rows 0 and 2 of x[0], where their totals
+// would be, are unspecified; the three live pairs' totals are the same bits.
+// (The 16-lane swap needs a partner register for w[1]: a dead one, the first
+// half of the 32-lane swap that made w[1], not a zero materialised per step.)
 template <bool Z01 = false>
 MC_DEV void lf_rs8(const float (&v)[8], float (&x)[2]) {
     float w[4];
+    uint32_t dead = 0;
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {  // lanes 0-31: v[2m] sums, lanes 32-63: v[2m+1]
-        if (Z01 && m == 0) {
-            w[0] = 0.0f;
-            continue;
-        }
+    for (int m = Z01 ? 1 : 0; m < 4; ++m) {  // lanes 0-31: v[2m] sums, lanes 32-63: v[2m+1]
         const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[2 * m]),
                                                         __float_as_uint(v[2 * m + 1]), false, false);
         w[m] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+        if (m == 1) dead = r[0];
     }
 #pragma unroll
     for (int n = 0; n < 2; ++n) {  // per 32-lane half: lanes 0-15 w[2n], 16-31 w[2n+1]
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(w[2 * n]),
-                                                        __float_as_uint(w[2 * n + 1]), false, false);
+        const auto r = __builtin_amdgcn_permlane16_swap(
+            (Z01 && n == 0) ? dead : __float_as_uint(w[2 * n]), __float_as_uint(w[2 * n + 1]),
+            false, false);
         float t = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-        t += dpp_row<0xB1>(t);
-        t += dpp_row<0x4E>(t);
-        t += dpp_row<0x141>(t);
-        t += dpp_row<0x140>(t);
+        t += lf_dpp<0xB1>(t);
+        t += lf_dpp<0x4E>(t);
+        t += lf_dpp<0x141>(t);
+        t += lf_dpp<0x140>(t);
         x[n] = t;
     }
 }
@@ -135,7 +154,13 @@ MC_DEV f2 lf_hi_minus(f2 xy, f2 th) {
 // parameter th) for both chains, packed FP32: d = x - th, s1 += d,
 // s2 = fma(d, d, s2), with the even and odd elements in separate packed
 // accumulators (two independent dependency chains each).
+// REREAD (one register slot, where the bounds are in SGPRs): the uniform
+// bounds are opaque per sweep, so the trip conditions derived from them are
+// scalar compares at their use (SCC), not per-launch lane masks that occupy
+// SGPR pairs and spill (a v_readlane per use in the step loop).
+template <bool REREAD = false>
 MC_DEV void lf_moments(const float* xv, int len, int lmin4, int lmax, f2 th, f2& s1, f2& s2) {
+    if constexpr (REREAD) asm volatile("" : "+s"(lmin4), "+s"(lmax));
     f2 a1[2], a2[2];
     // a register pair's elements broadcast by swizzle (op_sel on the pair,
     // no copy of the odd register); the first pair assigns the accumulators
@@ -274,7 +299,10 @@ MC_DEV LfTerms lf_terms(const MC_CONST LrTerm* tt, int nsweep, int ndirect) {
 // XL: the host found every exchange group's workgroups on one XCD
 // (host.h xcd_round_robin): records are published with L2-resident stores
 // (sliced.h granule_store_xcd), after an in-kernel check of the placement.
-template <int RS, int NSH, int NW, bool X1, int FORM, bool XL = false>
+// SPEC: launch constants the host resolved (LFS_* bits): their uniform
+// branches, live masks and scalar registers are compiled out; 0 reads them
+// all at run time.  (The own prior's kind needs no such bit: see o_m below.)
+template <int RS, int NSH, int NW, bool X1, int FORM, bool XL = false, int SPEC = 0>
 __global__ void __launch_bounds__(64 * NW)
 k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scalars* scal,
          float* st_q, float* st_g, float* samples, TraceDev tr, unsigned long long* xch,
@@ -367,12 +395,13 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
     for (int k = 1; k < kLrMaxShared; ++k) xg = (xo == k) ? P.shl[k] : xg;
     const int64_t xch_id = xc ? cc[1] : cc[0];
     const bool xlive = xon && (xc ? live[1] : live[0]);
-    const int rep = P.rep;                   // lanes per private parameter (lanes.h)
+    // lanes per private parameter (lanes.h); 1 at compile time under LFS_REP1
+    const int rep = (SPEC & LFS_REP1) ? 1 : P.rep;
     const bool lead = (j & (rep - 1)) == 0;  // this lane counts its parameters
     // a transformed shared parameter (lanes.h LrCtx::shxf) and the identity
     // terms over its raw value: a uniform branch, so programs without them
-    // run the same instructions as before
-    const bool hxf = P.has_xf != 0;
+    // run the same instructions as before (none of them under LFS_NOXF)
+    const bool hxf = (SPEC & LFS_NOXF) ? false : P.has_xf != 0;
     int xxf = P.shxf[0];
     float xid = P.shid[0];
 #pragma unroll
@@ -438,8 +467,18 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
     const LrOwn own = lr_own_prior(P.n_sterms, sst, xon ? 2 * xo + xc : 64, Dsh);
     const bool own_lp0 = own.on && slice == 0 && xc == 0;
     const bool own_lp1 = own.on && slice == 0 && xc == 1;
-    const float o_m = vpin(own.m), o_cinv2 = vpin(own.cinv2), o_c0l = vpin(own.c0l),
-                o_wn = vpin(own.wn);
+    // (a HalfNormal prior measures from 0: its loc is held as +0, and v - (+0)
+    // is v bit for bit, so the step's d = v - o_m needs no select on the kind)
+    const float o_m = vpin(own.hn ? 0.0f : own.m), o_cinv2 = vpin(own.cinv2),
+                o_c0l = vpin(own.c0l), o_wn = vpin(own.wn);
+    // the own prior's gradient at the shared parameter's value v: it depends on
+    // v alone, so it is formed where v is (drift_shared), off the path from
+    // the poll to the next position
+    auto own_grad = [&](float v) {
+        const float d = v - o_m;
+        const bool out = own.hn && !(v >= 0.0f);
+        return (out || !own.on) ? 0.0f : o_wn * -(d * o_cinv2);
+    };
     // per slot: the swept term's run (data pointer, length, full float4
     // groups of every lane) and the direct term's presence
     const float* xv[RS];
@@ -480,14 +519,14 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
              d_clogs = vpin(bc2(F.d_clogs));
     const f2 half = bc2(0.5f), one = bc2(1.0f);
     const float lp_const = vpin(P.lp_const);
-    // the swept terms' moment sums at the current point, both chains
+    // the swept terms' moment sums at the current point, both chains (a lane
+    // without elements never writes its sums: they stay the zeros they are
+    // declared with, so no zeros are materialised per sweep)
     auto sweep = [&](f2 (&s1)[RS], f2 (&s2)[RS]) {
 #pragma unroll
-        for (int r = 0; r < RS; ++r) {
-            s1[r] = (f2){0.f, 0.f};
-            s2[r] = (f2){0.f, 0.f};
-            if (len[r] > 0) lf_moments(xv[r], len[r], lmin4[r], lmax[r], q[r], s1[r], s2[r]);
-        }
+        for (int r = 0; r < RS; ++r)
+            if (len[r] > 0)
+                lf_moments<RS == 1>(xv[r], len[r], lmin4[r], lmax[r], q[r], s1[r], s2[r]);
     };
 
     const int L = cfg.num_leapfrog_steps;
@@ -646,6 +685,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                 q[r] = q[r] + e * pj;
             }
         };
+        float gown = 0.0f;  // the own prior's gradient at sh.v
         auto drift_shared = [&](bool second_half) {
             const float hg = xh * sh.g;
             float pj = sh.p;
@@ -662,8 +702,11 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             // is taken on the last step only, where log p is formed.
             sh.is = __builtin_amdgcn_rcpf(sh.v);
             sh.iv = sh.is * sh.is;
+            gown = vpin(own_grad(sh.v));  // for the step at this position
         };
         f2 M1[RS], M2[RS];
+#pragma unroll
+        for (int r = 0; r < RS; ++r) M1[r] = M2[r] = (f2){0.f, 0.f};
         drift_private(false);
         drift_shared(false);
         sweep(M1, M2);
@@ -792,13 +835,12 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             // the own prior of this lane's shared parameter (moment form with
             // the constant scale's reciprocals, as the sliced terms); its log p
             // enters slice 0's record
-            float g_own = 0.0f;
+            const float g_own = gown;  // (formed with sh.v, in drift_shared)
             {
-                const float v = sh.v;
-                const float d = own.hn ? v : v - o_m;
-                const bool out = own.hn && !(v >= 0.0f);
-                g_own = (out || !own.on) ? 0.0f : o_wn * -(d * o_cinv2);
                 if (lst) {
+                    const float v = sh.v;
+                    const float d = v - o_m;
+                    const bool out = own.hn && !(v >= 0.0f);
                     const float d2 = d * d;
                     const float lpe = out ? -__builtin_inff() : o_c0l - (0.5f * d2) * o_cinv2;
                     const float lp_own = o_wn * lpe;
@@ -962,10 +1004,9 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                 poll_issue();
                 ready = poll_eval();
             }
-            if (!ok) {
-                __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return false;
-            }
+            // (a timeout is reported once, after the trajectory's steps: the
+            // store's operands are not reloaded inside the step loop)
+            if (__builtin_expect(!ok, 0)) return false;
             MC_STAMP(3);
             __builtin_amdgcn_s_setprio(0);
             // slice sums: a fixed 16-lane DPP tree per pass; pair 4 ps + perm[r]
@@ -979,10 +1020,10 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                 for (int ps = 0; ps < NPASS; ++ps) {
                     float t = vals[ps];
                     if (ps < NPASS_V || kstep) {
-                        t += dpp_row<0xB1>(t);
-                        t += dpp_row<0x4E>(t);
-                        t += dpp_row<0x141>(t);
-                        t += dpp_row<0x140>(t);
+                        t += lf_dpp<0xB1>(t);
+                        t += lf_dpp<0x4E>(t);
+                        t += lf_dpp<0x141>(t);
+                        t += lf_dpp<0x140>(t);
                     }
                     tot[ps] = t;
                 }
@@ -1032,14 +1073,35 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             ok = step(0, std::integral_constant<int, 3>(), rtpar);
         } else {
             ok = step(0, std::integral_constant<int, 0>(), rtpar);
-            for (int l = 1; ok && l < L - 1; ++l) {
-                if (X1) ok = step(l, std::integral_constant<int, 1>(), rtpar);
-                else if (epoch & 1) ok = step(l, std::integral_constant<int, 1>(), std::integral_constant<int, 0>());
-                else ok = step(l, std::integral_constant<int, 1>(), std::integral_constant<int, 1>());
+            const std::integral_constant<int, 1> mid;
+            if (X1) {
+                for (int l = 1; ok && l < L - 1; ++l) ok = step(l, mid, rtpar);
+            } else {
+                // the intermediate steps, two per loop trip: line parity 0 then
+                // parity 1, straight-line, so every loop-carried value is in
+                // the same register at the head and at the latch (no dispatch
+                // on the parity, no copies between the two bodies' registers).
+                // One aligning step first when the tags start on the other
+                // parity, one trailing step when the count is odd.
+                const std::integral_constant<int, 0> par0;
+                const std::integral_constant<int, 1> par1;
+                int n = L - 2;
+                if (n > 0 && !(epoch & 1)) {  // (the next tag is odd: parity 1)
+                    ok = step(1, mid, par1);
+                    --n;
+                }
+                for (; __builtin_expect(ok, 1) && n >= 2; n -= 2) {
+                    ok = step(1, mid, par0);
+                    if (__builtin_expect(ok, 1)) ok = step(1, mid, par1);
+                }
+                if (ok && n == 1) ok = step(1, mid, par0);
             }
             if (ok) ok = step(L - 1, std::integral_constant<int, 2>(), rtpar);
         }
-        if (!ok) break;
+        if (!ok) {  // an exchange timeout in one of the steps
+            __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+        }
         // ---- accept / adapt (identical in every slice of the block) ------------
         float k1s[2] = {0.f, 0.f};
         {

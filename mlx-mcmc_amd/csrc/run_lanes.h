@@ -91,6 +91,18 @@ inline int launch_hmc_lr(const mc_program* p, const mc_run_config* cfg, void* st
         if (fast && forms && p->lr.form == HIER) {
             kern = k_hmc_lf<RS, lf_nroles(HIER), NW, X1, HIER>;
             kern_xl = X1 ? kern : k_hmc_lf<RS, lf_nroles(HIER), NW, X1, HIER, true>;
+            // the launch constants of the common layout, compiled in: one
+            // lane per private parameter, no transformed shared parameter
+            // at one register slot per lane (the bench shapes; every other
+            // combination reads them at run time, above: few instantiations)
+            if constexpr (RS == 1) {
+                constexpr int PLAIN = LFS_REP1 | LFS_NOXF;
+                if (p->lr.rep == 1 && p->lr.has_xf == 0) {
+                    kern = k_hmc_lf<RS, lf_nroles(HIER), NW, X1, HIER, false, PLAIN>;
+                    kern_xl =
+                        X1 ? kern : k_hmc_lf<RS, lf_nroles(HIER), NW, X1, HIER, true, PLAIN>;
+                }
+            }
         }
         if (fast && forms && p->lr.form == LF_DIR) {
             kern = k_hmc_lf<RS, lf_nroles(LF_DIR), NW, X1, LF_DIR>;
