@@ -1355,6 +1355,16 @@ class Program:
         """True when a lane-resident launch runs the fast-form kernel k_hmc_lf."""
         return _lib.load().mc_program_lanes_fast(self.handle) == 1
 
+    @property
+    def lane_slots(self) -> int:
+        """Register slots per lane of the lane-resident plan (0: no plan)."""
+        return int(_lib.load().mc_program_lane_slots(self.handle))
+
+    @property
+    def lane_rep(self) -> int:
+        """Lanes per private parameter of the lane-resident plan (0: no plan)."""
+        return int(_lib.load().mc_program_lane_rep(self.handle))
+
     def __del__(self):
         h = getattr(self, "handle", None)
         if h is not None and h.value:

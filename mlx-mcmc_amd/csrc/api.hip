@@ -1342,6 +1342,16 @@ extern "C" int32_t mc_program_lanes_fast(const mc_program* p) {
     return (k == 2 && p->lr.fast && lanes_fast_enabled()) ? 1 : 0;
 }
 
+extern "C" int32_t mc_program_lane_slots(const mc_program* p) {
+    if (!p) return -1;
+    return p->lr.ok ? p->lr.rs : 0;
+}
+
+extern "C" int32_t mc_program_lane_rep(const mc_program* p) {
+    if (!p) return -1;
+    return p->lr.ok ? p->lr.rep : 0;
+}
+
 extern "C" int32_t mc_program_num_slices(const mc_program* p) { return p ? p->sl.S : -1; }
 
 extern "C" const char* mc_program_kernel_note(const mc_program* p) {
