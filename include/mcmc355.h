@@ -280,10 +280,13 @@ int32_t mc_program_lanes_fast(const mc_program* prog);
 /* The lane-resident plan's geometry, for tests and diagnostics: register
  * slots per lane (1, 2 or 4: private parameters per slice / 64, rounded up)
  * and lanes per private parameter (1, or a power of two up to 16 when a
- * slice holds at most 32 of them; MC_LANES_REP caps it).  0 when the
+ * slice holds at most 32 of them; MC_LANES_REP caps it), and the widest
+ * bundle of private parameters one element of a gathered expression term
+ * reads (alpha[g] + beta[g] * x: 2; 0 without such a term).  0 when the
  * program has no lane-resident plan, -1 on a null program.                  */
 int32_t mc_program_lane_slots(const mc_program* prog);
 int32_t mc_program_lane_rep(const mc_program* prog);
+int32_t mc_program_lane_bundle(const mc_program* prog);
 /* Why the program's HMC launches do not run the lane-resident kernel (e.g.
  * "lane-resident kernel: more than 4 broadcast parameters"), or "" when they
  * do or no plan was attempted; valid until the next set_slices /

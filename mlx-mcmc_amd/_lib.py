@@ -200,6 +200,7 @@ SIGNATURES = [
     ("mc_program_lanes_fast", ctypes.c_int32, [_VP]),
     ("mc_program_lane_slots", ctypes.c_int32, [_VP]),
     ("mc_program_lane_rep", ctypes.c_int32, [_VP]),
+    ("mc_program_lane_bundle", ctypes.c_int32, [_VP]),
     ("mc_program_kernel_note", ctypes.c_char_p, [_VP]),
     ("mc_program_nuts_lanes", ctypes.c_int32, [_VP, ctypes.c_int32]),
     ("mc_logp_grad", ctypes.c_int, [_VP, ctypes.c_int64, _VP, _VP, _VP, _VP]),

@@ -1365,6 +1365,13 @@ class Program:
         """Lanes per private parameter of the lane-resident plan (0: no plan)."""
         return int(_lib.load().mc_program_lane_rep(self.handle))
 
+    @property
+    def lane_bundle(self) -> int:
+        """Widest bundle of private parameters one element of a gathered
+        expression term reads on the lane-resident plan (alpha[g] + beta[g] * x:
+        2); 0 when the plan has no such term, or there is no plan."""
+        return int(_lib.load().mc_program_lane_bundle(self.handle))
+
     def __del__(self):
         h = getattr(self, "handle", None)
         if h is not None and h.value:
@@ -1391,7 +1398,8 @@ def _own_prior_like(t: Term) -> bool:
             and t.scale.kind == _lib.MC_OP_CONST)
 
 
-def affine_as_expressions(model: TracedModel, scalars: bool = False) -> Optional[TracedModel]:
+def affine_as_expressions(model: TracedModel, scalars: bool = False,
+                          vectors: bool = False) -> Optional[TracedModel]:
     """The same model with every fused affine-loc term (``Normal(a + b * x,
     s)``, mc_affine) rebuilt as an expression term of the same per-element
     arithmetic (its MC_EX_NORMAL_LP node over ADD(a, MUL(b, x))), the other
@@ -1401,7 +1409,14 @@ def affine_as_expressions(model: TracedModel, scalars: bool = False) -> Optional
     tape.  scalars: also every scalar term those kernels cannot take as a
     shared parameter's own prior (``Exponential(1).log_prob(sigma)``, a
     second prior on one parameter, a prior with a parameter argument) — the
-    kernels evaluate scalar terms only as own priors."""
+    kernels evaluate scalar terms only as own priors.  vectors: also every
+    per-element term over a private parameter vector (``Normal(mu_a,
+    2.0).log_prob(alpha)``, a grouped likelihood), as an expression term with a
+    parameter-vector or gather leaf: beside a gathered-parameter likelihood
+    (``alpha[g] + beta[g] * x``) the sliced kernels' fast form takes at most one
+    swept and one direct fused term, the lane expression code any number
+    (csrc/host.h expr_term_class: the prior joins the likelihood's bundles)."""
+    vec_kinds = (_lib.MC_OP_PVEC, _lib.MC_OP_GATHER)
     owned = set()
     convert = []
     for t in model.terms:
@@ -1412,6 +1427,10 @@ def affine_as_expressions(model: TracedModel, scalars: bool = False) -> Optional
             if own:
                 owned.add(t.value.param_offset)
             c = not own and t.src is not None and t.src[0] in _EXPR_DIST
+        if (vectors and not c and t.n > 1 and t.dist != _lib.MC_DIST_EXPR
+                and t.src is not None and t.src[0] in _EXPR_DIST
+                and any(o.kind in vec_kinds for o in (t.value, t.loc, t.scale))):
+            c = True
         convert.append(c)
     if not any(convert):
         return None
@@ -1434,6 +1453,10 @@ def affine_as_expressions(model: TracedModel, scalars: bool = False) -> Optional
     return out
 
 
+# the alternative forms nuts_program / mh_program try, in order: (scalars, vectors)
+_ALT_FORMS = ((False, False), (True, False), (False, True), (True, True))
+
+
 def nuts_program(prog: "Program", max_tree_depth: int = 10) -> "Program":
     """The program NUTS runs: `prog`, or — when its affine-loc terms (and,
     failing that, its scalar terms other than own priors) keep NUTS on the
@@ -1442,9 +1465,9 @@ def nuts_program(prog: "Program", max_tree_depth: int = 10) -> "Program":
     `prog`: the lane kernel k_hmc_lr runs affine and generic scalar terms.)"""
     if prog.nuts_kernel(max_tree_depth) != "tape":
         return prog
-    for scalars in (False, True):
+    for scalars, vectors in _ALT_FORMS:
         try:
-            alt = affine_as_expressions(prog.model, scalars)
+            alt = affine_as_expressions(prog.model, scalars, vectors)
         except TraceError:
             continue
         if alt is None:
@@ -1466,9 +1489,9 @@ def mh_program(prog: "Program") -> "Program":
     lib = _lib.load()
     if lib.mc_program_mh_sliced(prog.handle) == 1:
         return prog
-    for scalars in (False, True):
+    for scalars, vectors in _ALT_FORMS:
         try:
-            alt = affine_as_expressions(prog.model, scalars)
+            alt = affine_as_expressions(prog.model, scalars, vectors)
         except TraceError:
             continue
         if alt is None:

@@ -218,16 +218,22 @@ struct SlPartition {
     std::vector<std::vector<int>> priv;   // per slice: its private parameters
     std::vector<int> shl;                 // shared parameters by ordinal
     std::vector<std::vector<std::vector<int64_t>>> elems;  // [slice][term] element ids
+    // grouped expression terms (host.h expr_term_class): per term its distinct
+    // parameter vectors' offsets and its element -> group map (empty: not
+    // grouped); per parameter the lowest member of its bundle (itself: alone)
+    // and its position in the bundle
+    std::vector<std::vector<int32_t>> gvec, gmap;
+    std::vector<int> bfirst, bpos;
+    bool grouped = false;
 };
 
 
 static int plan_slices(mc_program* p, int S, SlicePlan& P, SlPartition* part = nullptr) {
     const std::vector<DevTerm>& raw = p->raw;
-    if (has_expr(p) && !expr_lanes_ok(p))
-        return fail(MC_ERR_UNSUPPORTED, "expression terms other than data / broadcast "
-                    "parameter / constant leaves (a parameter vector, a gather, more than %d "
-                    "data leaves) run on the chain-per-workgroup kernels (not sliceable)",
-                    kLrExprData);
+    if (has_expr(p)) {
+        const std::string why = expr_lanes_why(p);
+        if (!why.empty()) return fail(MC_ERR_UNSUPPORTED, "%s", why.c_str());
+    }
     if (has_affine(p) && !affine_lanes_ok(p))
         return fail(MC_ERR_UNSUPPORTED, "affine loc operands other than `loc + b * x` over "
                     "data x (x a parameter vector, a non-Normal term, a per-element scale) run "
@@ -251,6 +257,59 @@ static int plan_slices(mc_program* p, int S, SlicePlan& P, SlPartition* part = n
                                 "term %d has two per-element parameter operands: not sliceable", t);
                 ppr[t] = a;
             }
+    // grouped expression terms and the bundles of private parameters their
+    // elements read (alpha_g, beta_g): bundles that share a parameter merge
+    std::vector<std::vector<int32_t>> gvec(nT), gmap(nT);
+    std::vector<int> bfirst(D), bpos(D, 0);
+    std::iota(bfirst.begin(), bfirst.end(), 0);
+    bool grouped = false;
+    std::vector<std::vector<int>> bmem;  // per bundle first: its members, ascending
+    for (int t = 0; t < nT; ++t)
+        if (raw[t].dist == MC_DIST_EXPR &&
+            expr_term_class(p, raw[t], &gvec[t], &gmap[t], nullptr) == 1)
+            grouped = true;
+    if (grouped) {
+        std::vector<int> root(D);
+        std::iota(root.begin(), root.end(), 0);
+        auto find = [&](int x) {
+            while (root[x] != x) x = root[x] = root[root[x]];
+            return x;
+        };
+        // a vector's bundles cover every group of its range, with elements or
+        // not (an empty group's alpha_g and beta_g still sit together, so a
+        // term over beta alone sees one slot offset): the range is the largest
+        // group count of any term that reads the vector, shared by the vectors
+        // read together
+        std::map<int32_t, int32_t> vrange;
+        for (int pass = 0; pass < 3; ++pass)
+            for (int t = 0; t < nT; ++t) {
+                if (gmap[t].empty()) continue;
+                int32_t r = *std::max_element(gmap[t].begin(), gmap[t].end()) + 1;
+                for (int32_t v : gvec[t]) r = std::max(r, vrange[v]);
+                for (int32_t v : gvec[t]) vrange[v] = r;
+            }
+        for (int t = 0; t < nT; ++t)
+            for (size_t v = 1; v < gvec[t].size(); ++v)
+                for (int32_t g = 0; g < vrange[gvec[t][0]]; ++g) {
+                    if (gvec[t][0] + g >= D || gvec[t][v] + g >= D) break;
+                    const int a = find(gvec[t][0] + g), b = find(gvec[t][v] + g);
+                    if (a != b) root[std::max(a, b)] = std::min(a, b);  // (the root: the lowest)
+                }
+        std::vector<int> count(D, 0);
+        bmem.assign(D, std::vector<int>());
+        for (int j = 0; j < D; ++j) {
+            bfirst[j] = find(j);
+            bpos[j] = count[bfirst[j]]++;
+            bmem[bfirst[j]].push_back(j);
+        }
+        for (int j = 0; j < D; ++j)
+            if (count[bfirst[j]] > kLrMaxSlots)
+                return fail(MC_ERR_UNSUPPORTED, "a bundle of %d private parameters read together "
+                            "by gathered expression terms (more than %d) does not fit a lane's "
+                            "register slots (not sliceable)", count[bfirst[j]], kLrMaxSlots);
+    }
+    // the parameter whose owner takes element i of a grouped expression term
+    auto gx_param = [&](int t, int64_t i) { return bfirst[gvec[t][0] + gmap[t][(size_t)i]]; };
     // shared (broadcast) parameters and the private parameters' costs
     std::vector<char> shared(D, 0);
     for (const DevTerm& t : raw) {
@@ -270,6 +329,20 @@ static int plan_slices(mc_program* p, int S, SlicePlan& P, SlPartition* part = n
                 const int64_t j = pp_index(raw[t], ppr[t], i, ip);
                 if (!shared[j]) cost[j] += 1;
             }
+    for (int t = 0; t < nT; ++t)
+        if (!gmap[t].empty())
+            for (int32_t g : gmap[t]) {
+                for (int32_t v : gvec[t])
+                    if (shared[v + g])
+                        return fail(MC_ERR_UNSUPPORTED, "an expression term gathers a parameter "
+                                    "that other terms read as a broadcast scalar: not sliceable");
+                cost[gvec[t][0] + g] += 1;
+            }
+    // (a bundle is indivisible: its members' summed cost, at its lowest member)
+    std::vector<int64_t> bcost(cost);
+    if (grouped)
+        for (int j = 0; j < D; ++j)
+            if (bfirst[j] != j) bcost[bfirst[j]] += cost[j];
     int64_t total = 0;
     for (int j = 0; j < D; ++j)
         if (!shared[j]) total += cost[j];
@@ -284,11 +357,15 @@ static int plan_slices(mc_program* p, int S, SlicePlan& P, SlPartition* part = n
                 shl.push_back(j);
                 continue;
             }
-            const int s = (int)std::min<int64_t>(S - 1, (2 * run + cost[j]) * S / (2 * std::max<int64_t>(total, 1)));
-            owner[j] = s;
-            lidx[j] = (int)priv[s].size();
-            priv[s].push_back(j);
-            run += cost[j];
+            if (bfirst[j] != j) continue;  // (placed with its bundle, below)
+            const int s = (int)std::min<int64_t>(S - 1, (2 * run + bcost[j]) * S / (2 * std::max<int64_t>(total, 1)));
+            const std::vector<int> alone(1, j);
+            for (int m : grouped ? bmem[j] : alone) {  // the bundle's members, ascending
+                owner[m] = s;
+                lidx[m] = (int)priv[s].size();
+                priv[s].push_back(m);
+            }
+            run += bcost[j];
         }
     }
     // the transform of each shared parameter: every transformed use agrees;
@@ -432,6 +509,8 @@ static int plan_slices(mc_program* p, int S, SlicePlan& P, SlPartition* part = n
             if (ppr[t] >= 0) {
                 const int64_t j = pp_index(raw[t], ppr[t], i, ip);
                 s = shared[j] ? 0 : owner[j];
+            } else if (!gmap[t].empty()) {
+                s = owner[gx_param(t, i)];
             } else if (n < 256) {
                 s = t % S;  // small terms go whole to one slice, round robin
             } else {
@@ -450,6 +529,11 @@ static int plan_slices(mc_program* p, int S, SlicePlan& P, SlPartition* part = n
         part->priv = priv;
         part->shl = shl;
         part->elems = elems;
+        part->gvec = gvec;
+        part->gmap = gmap;
+        part->bfirst = bfirst;
+        part->bpos = bpos;
+        part->grouped = grouped;
     }
 
     struct Run {
@@ -820,6 +904,67 @@ static int plan_lanes(const mc_program* p, const SlicePlan& SP, const SlPartitio
         rs = std::max(rs, need);
     }
     if (rs == 3) rs = 4;
+    // One slice's private parameters -> (lane group, slot): whole bundles (a
+    // parameter alone: a bundle of one), heaviest first onto the least loaded
+    // lane group with free consecutive slots for all its members.  ln / sl per
+    // position in part.priv[s]; false when a bundle finds no lane.
+    auto deal = [&](int s, int rs_, int ngroups_, std::vector<int>& ln, std::vector<int>& sl) {
+        const std::vector<int>& pv = part.priv[s];
+        std::vector<int64_t> cost(pv.size(), 0);
+        std::vector<int> lpos(p->D, -1);
+        for (size_t k = 0; k < pv.size(); ++k) lpos[pv[k]] = (int)k;
+        for (int t = 0; t < nT; ++t) {
+            if (part.scalar[t]) continue;
+            if (part.ppr[t] >= 0)
+                for (int64_t i : part.elems[s][t]) cost[lpos[pp_index(raw[t], part.ppr[t], i, ip)]]++;
+            else if (!part.gmap[t].empty())
+                for (int64_t i : part.elems[s][t])
+                    cost[lpos[part.bfirst[part.gvec[t][0] + part.gmap[t][(size_t)i]]]]++;
+        }
+        // (a bundle's members follow its first in priv[s], plan_slices)
+        std::vector<int> items, width;
+        std::vector<int64_t> icost;
+        for (size_t k = 0; k < pv.size(); ++k) {
+            if (part.bfirst[pv[k]] == pv[k]) {
+                items.push_back((int)k);
+                width.push_back(1);
+                icost.push_back(cost[k]);
+            } else {
+                ++width.back();
+                icost.back() += cost[k];
+            }
+        }
+        std::vector<int> ord(items.size());
+        std::iota(ord.begin(), ord.end(), 0);
+        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return icost[a] > icost[b]; });
+        std::vector<int64_t> load(ngroups_, 0);
+        std::vector<int> used(ngroups_, 0);
+        ln.assign(pv.size(), -1);
+        sl.assign(pv.size(), -1);
+        for (int it : ord) {
+            int best = -1;
+            for (int l = 0; l < ngroups_; ++l)
+                if (used[l] + width[it] <= rs_ && (best < 0 || load[l] < load[best])) best = l;
+            if (best < 0) return false;
+            for (int m = 0; m < width[it]; ++m) {
+                ln[items[it] + m] = best;
+                sl[items[it] + m] = used[best]++;
+            }
+            load[best] += icost[it];
+        }
+        return true;
+    };
+    if (part.grouped) {  // the slots every slice's bundles need (whole bundles per lane)
+        std::vector<int> ln, sl;
+        for (;;) {
+            bool fit = true;
+            for (int s = 0; s < S && fit; ++s) fit = deal(s, rs, 64, ln, sl);
+            if (fit) break;
+            if (rs >= kLrMaxSlots)
+                return no("the bundles of private parameters do not fit the lanes' register slots");
+            rs = rs == 1 ? 2 : 4;
+        }
+    }
     // replication (lanes.h LrCtx::rep): with at most 32 private parameters per
     // slice, each is dealt to a group of `rep` lanes (the largest power of two
     // <= 16 that still fits every parameter) and its elements are split over
@@ -827,7 +972,7 @@ static int plan_lanes(const mc_program* p, const SlicePlan& SP, const SlPartitio
     // README "Small" shape: 7 groups of ~143 observations, 7 busy lanes of 64).
     // MC_LANES_REP=<k> caps it (1: off; A/B and tests).
     int rep = 1;
-    if (rs == 1) {
+    if (rs == 1 && !part.grouped) {  // (a plan with grouped expression terms: rep = 1)
         size_t maxp = 1;
         for (int s = 0; s < S; ++s) maxp = std::max(maxp, part.priv[s].size());
         int np2 = 1;
@@ -844,6 +989,30 @@ static int plan_lanes(const mc_program* p, const SlicePlan& SP, const SlPartitio
         for (int64_t i = 0; i < raw[t].n; ++i)
             if (part.shared[pp_index(raw[t], part.ppr[t], i, ip)])
                 return no("a per-element operand reads a broadcast parameter");
+    }
+    // the widest bundle a grouped expression term reads, and each gathered
+    // leaf's slot offset inside its bundle: one value per leaf over all elements
+    L.bundle = 0;
+    L.gx_off.assign(p->rnodes.size(), -1);
+    if (part.grouped) {
+        std::vector<int> bwidth(p->D, 0);
+        for (int j = 0; j < p->D; ++j) bwidth[part.bfirst[j]]++;
+        for (int t = 0; t < nT; ++t) {
+            if (part.gmap[t].empty()) continue;
+            for (int k = 0; k < raw[t].expr_n; ++k) {
+                const DevExprNode& d = p->rnodes[raw[t].expr_base + k];
+                if (d.op != MC_EX_LEAF || (d.leaf.kind != MC_OP_PVEC && d.leaf.kind != MC_OP_GATHER))
+                    continue;
+                int32_t& off = L.gx_off[raw[t].expr_base + k];
+                for (int32_t g : part.gmap[t]) {
+                    const int j = d.leaf.poff + g;
+                    L.bundle = std::max(L.bundle, bwidth[part.bfirst[j]]);
+                    if (off >= 0 && off != part.bpos[j])
+                        return no("a gathered leaf sits at different slots of its elements' bundles");
+                    off = part.bpos[j];
+                }
+            }
+        }
     }
     L.rs = rs;
     L.rep = rep;
@@ -862,28 +1031,16 @@ static int plan_lanes(const mc_program* p, const SlicePlan& SP, const SlPartitio
     for (int s = 0; s < S; ++s) {
         // ---- parameters -> (lane, slot) ----
         const std::vector<int>& pv = part.priv[s];
-        std::vector<int64_t> cost(pv.size(), 0);
-        std::vector<int> lpos(p->D, -1);
-        for (size_t k = 0; k < pv.size(); ++k) lpos[pv[k]] = (int)k;
-        for (int t = 0; t < nT; ++t) {
-            if (part.scalar[t] || part.ppr[t] < 0) continue;
-            for (int64_t i : part.elems[s][t]) cost[lpos[pp_index(raw[t], part.ppr[t], i, ip)]]++;
-        }
-        std::vector<int> ord(pv.size());
-        std::iota(ord.begin(), ord.end(), 0);
-        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-        // (lane groups of `rep` lanes; lane_of = the group's leader lane)
-        std::vector<int64_t> load(ngroups, 0);
-        std::vector<int> used(ngroups, 0);
-        for (int k : ord) {
-            int best = -1;
-            for (int l = 0; l < ngroups; ++l)
-                if (used[l] < rs && (best < 0 || load[l] < load[best])) best = l;
-            lane_of[pv[k]] = best * rep;
-            slot_of_p[pv[k]] = used[best]++;
-            load[best] += cost[k];
-            for (int x = 0; x < rep; ++x)
-                L.gidx[((size_t)s * kLrMaxSlots + slot_of_p[pv[k]]) * 64 + best * rep + x] = pv[k];
+        {
+            std::vector<int> ln, sl;
+            if (!deal(s, rs, ngroups, ln, sl)) return no("a private parameter finds no lane");
+            // (lane groups of `rep` lanes; lane_of = the group's leader lane)
+            for (size_t k = 0; k < pv.size(); ++k) {
+                lane_of[pv[k]] = ln[k] * rep;
+                slot_of_p[pv[k]] = sl[k];
+                for (int x = 0; x < rep; ++x)
+                    L.gidx[((size_t)s * kLrMaxSlots + sl[k]) * 64 + ln[k] * rep + x] = pv[k];
+            }
         }
         // ---- terms: the swept ones (lanes.h kLrSweep) first ----
         while (L.data.size() % 4) L.data.push_back(0.0f);
@@ -953,6 +1110,9 @@ static int plan_lanes(const mc_program* p, const SlicePlan& SP, const SlPartitio
                 lt.expr_base = rt.expr_base;
                 lt.expr_n = rt.expr_n;
                 L.has_expr = 1;
+                // a grouped term: tiled by the (lane, first slot) of its
+                // elements' bundles; its vectors' slot offsets inside them
+                lt.kb = (int32_t)part.gvec[t].size();
             }
             // element lists per (slot, lane), in element order
             std::vector<std::vector<int64_t>> lists((size_t)kLrMaxSlots * 64);
@@ -980,6 +1140,13 @@ static int plan_lanes(const mc_program* p, const SlicePlan& SP, const SlPartitio
                                 f += len;
                             }
                         }
+            } else if (!part.gmap[t].empty()) {  // a grouped expression term
+                for (int64_t i : E) {
+                    const int g = part.bfirst[part.gvec[t][0] + part.gmap[t][(size_t)i]];
+                    const int r = slot_of_p[g];
+                    lists[(size_t)r * 64 + lane_of[g]].push_back(i);
+                    nslot = std::max(nslot, r + 1);
+                }
             } else {  // chunk term: contiguous near-equal chunks over the lanes (slot 0)
                 const int64_t nE = (int64_t)E.size(), nch = std::min<int64_t>(64, nE);
                 int64_t f = 0;
@@ -1026,7 +1193,7 @@ static int plan_lanes(const mc_program* p, const SlicePlan& SP, const SlPartitio
                 int e = 0;
                 std::vector<int64_t> seen;
                 for (int k = 0; k < rt.expr_n; ++k) {
-                    const DevExprNode& d = p->nodes[rt.expr_base + k];
+                    const DevExprNode& d = p->rnodes[rt.expr_base + k];
                     if (d.op != MC_EX_LEAF || d.leaf.kind != MC_OP_DATA) continue;
                     if (std::find(seen.begin(), seen.end(), d.leaf.pool) != seen.end()) continue;
                     seen.push_back(d.leaf.pool);
@@ -1177,7 +1344,6 @@ static int64_t program_elements(const mc_program* p) {
 // 8 - 64 K elements: 8 slices (one wave per SIMD, every CU busy at 256
 // chains; the D = 100 / N = 10 k model: 165 -> 185 M steps/s against 4
 // slices, 79 M with 16, profiles/r4/slices).
-static constexpr int64_t kLrAutoMinElements = 2048;
 static int auto_slices(const mc_program* p) {
     if ((has_expr(p) && !expr_lanes_ok(p)) || (has_affine(p) && !affine_lanes_ok(p)) ||
         (has_transform(p) && !transform_on_shared_only(p)))
@@ -1352,6 +1518,11 @@ extern "C" int32_t mc_program_lane_rep(const mc_program* p) {
     return p->lr.ok ? p->lr.rep : 0;
 }
 
+extern "C" int32_t mc_program_lane_bundle(const mc_program* p) {
+    if (!p) return -1;
+    return p->lr.ok ? p->lr.bundle : 0;
+}
+
 extern "C" int32_t mc_program_num_slices(const mc_program* p) { return p ? p->sl.S : -1; }
 
 extern "C" const char* mc_program_kernel_note(const mc_program* p) {
@@ -1398,7 +1569,7 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
                            const mc_expr_node* nodes, int32_t n_nodes, int32_t n_params,
                            int64_t n_data, int64_t n_index, std::vector<float>& dpool,
                            std::vector<int32_t>& ipool, std::vector<DevExprNode>& gnodes,
-                           DevTerm& dt, int wpc) {
+                           std::vector<DevExprNode>& rnodes, DevTerm& dt, int wpc) {
     // (leaf ranges are checked against the caller's pools, n_data / n_index:
     // dpool / ipool already hold the library's own tiled copies of earlier terms)
     if (src.affine < 1 || src.affine > n_exprs)
@@ -1562,6 +1733,9 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
             return fail(MC_ERR_UNSUPPORTED, "term %d: more than 16 overlapping vector leaves", t);
         dt.npass = std::max<int>(1, (int)pr.size());
     }
+    // (the nodes as validated: the slice / lane planners tile a gathered term
+    // themselves, from the caller's pools in element order)
+    rnodes.insert(rnodes.end(), en.begin(), en.end());
     if (prim_pool >= 0) {
         // order the term by the index (stable), then tile it by runs
         bool sorted = true;
@@ -1642,7 +1816,7 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
     std::vector<float> dpool(data, data + n_data);
     std::vector<int32_t> ipool(index, index + n_index);
     std::vector<DevTerm> dts, raws;
-    std::vector<DevExprNode> gnodes;
+    std::vector<DevExprNode> gnodes, rnodes;
     int64_t max_n = 0;
     for (int32_t t = 0; t < n_terms; ++t) max_n = std::max<int64_t>(max_n, terms[t].n);
     const int wpc = choose_wpc(max_n);
@@ -1657,7 +1831,8 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
         std::memset(&dt, 0, sizeof(dt));
         if (src.dist == MC_DIST_EXPR) {
             const int rc = build_expr_term(t, src, exprs, n_exprs, nodes, n_nodes, n_params,
-                                           n_data, n_index, dpool, ipool, gnodes, dt, wpc);
+                                           n_data, n_index, dpool, ipool, gnodes, rnodes, dt,
+                                           wpc);
             if (rc) return rc;
             raws.push_back(dt);
             dts.push_back(dt);
@@ -2011,6 +2186,7 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
     p->terms = dts;
     p->raw = raws;
     p->nodes = gnodes;
+    p->rnodes = rnodes;
     p->ex = !gnodes.empty();
     p->h_data = dpool;
     p->h_index = ipool;

@@ -101,6 +101,10 @@ struct LanePlan {
     int nuts_expr = 0;   // LS_EXPR terms beside a fast form (every other term swept /
                          // direct, every scalar term an own prior): the JIT-compiled
                          // run-time form of k_nuts_sl takes the program
+    int bundle = 0;      // grouped expression terms (LrTerm::kb): the widest bundle of
+                         // private parameters one element reads (alpha_g, beta_g: 2), else 0
+    std::vector<int32_t> gx_off;  // per program node: a gathered leaf's slot offset
+                                  // inside its bundle (jit.hip gen_lane_term), else -1
     std::string why;     // why it does not qualify
     std::vector<LrTerm> terms;
     std::vector<float> data;
@@ -124,6 +128,9 @@ struct mc_program {
     std::vector<DevTerm> terms;
     DevTerm* d_terms = nullptr;
     std::vector<DevExprNode> nodes;  // expression-term nodes (DevTerm::expr_base)
+    std::vector<DevExprNode> rnodes;  // the same nodes as validated, before a gathered
+                                      // term's leaves are sorted and tiled for the tape
+                                      // (original pools, element order): the planners' input
     bool ex = false;                 // has expression terms: the EX kernel instantiations
     DevExprNode* d_nodes = nullptr;
     float* d_data = nullptr;
@@ -238,31 +245,98 @@ inline bool affine_lanes_ok(const mc_program* p) {
 }
 // Expression terms the lane-resident kernel takes (lanes.h LS_EXPR, code
 // generated per program by the expression JIT): leaves data, broadcast
-// parameters and constants only — no parameter vectors or gathers — with at
-// least one data array and at most kLrExprData of them, one pass.  Every term
-// of the program must qualify (else the program stays on the tape kernels).
-inline bool expr_lanes_ok(const mc_program* p) {
+// parameters and constants, with at least one data array and at most
+// kLrExprData of them, one pass — a chunk term, its elements dealt evenly —
+// or, beside those, parameter-vector and gather leaves that all read through
+// one element -> group map (a PVEC leaf: the identity): a grouped term, its
+// elements tiled by the (lane, slot) that owns the group's bundle of private
+// parameters (alpha_g, beta_g; api.hip plan_lanes).  expr_term_class: 0 a
+// chunk term, 1 a grouped term (its distinct vectors' offsets into *vecs, its
+// map into *gmap), -1 neither (why).  Every term of the program must qualify
+// (else the program stays on the tape kernels).
+inline int expr_term_class(const mc_program* p, const DevTerm& t, std::vector<int32_t>* vecs,
+                           std::vector<int32_t>* gmap, std::string* why) {
+    auto no = [&](const char* w) {
+        if (why) *why = w;
+        return -1;
+    };
+    if (t.npass != 1 || t.expr_n < 1) return no("an expression term swept in several passes");
+    const std::vector<int32_t>& ip = p->h_index;
+    std::vector<int64_t> arrays;  // distinct data arrays (one LDS tile each)
+    std::vector<int32_t> vs;
+    const DevExprNode* first = nullptr;  // the first vector leaf: the term's map
+    for (int k = 0; k < t.expr_n; ++k) {
+        const DevExprNode& d = p->rnodes[t.expr_base + k];
+        if (d.op != MC_EX_LEAF) continue;
+        if (d.leaf.kind == MC_OP_DATA) {
+            if (std::find(arrays.begin(), arrays.end(), d.leaf.pool) == arrays.end())
+                arrays.push_back(d.leaf.pool);
+        } else if (d.leaf.kind == MC_OP_PVEC || d.leaf.kind == MC_OP_GATHER) {
+            if (std::find(vs.begin(), vs.end(), d.leaf.poff) == vs.end()) vs.push_back(d.leaf.poff);
+            if (!first) {
+                first = &d;
+                continue;
+            }
+            for (int64_t i = 0; i < t.n; ++i) {
+                const int64_t a = first->leaf.kind == MC_OP_PVEC ? i : ip[first->leaf.pool + i];
+                const int64_t b = d.leaf.kind == MC_OP_PVEC ? i : ip[d.leaf.pool + i];
+                if (a != b) return no("an expression term gathers through two different index maps");
+            }
+        } else if (d.leaf.kind != MC_OP_CONST && d.leaf.kind != MC_OP_PSCALAR) {
+            return no("an expression leaf the lane kernels do not take");
+        }
+    }
+    if (arrays.empty() || (int)arrays.size() > kLrExprData)
+        return no("an expression term needs 1 .. 6 data arrays");
+    if (!first) return 0;
+    if (vecs) *vecs = vs;
+    if (gmap) {
+        gmap->resize((size_t)t.n);
+        for (int64_t i = 0; i < t.n; ++i)
+            (*gmap)[(size_t)i] = first->leaf.kind == MC_OP_PVEC ? (int32_t)i : ip[first->leaf.pool + i];
+    }
+    return 1;
+}
+// programs below the slicing threshold stay on the tape: a grouped expression
+// program is planned onto the lanes from this many elements on
+static constexpr int64_t kLrAutoMinElements = 2048;
+// Why the program's expression terms do not take the lane layout ("" when
+// they do, or when it has none).
+inline std::string expr_lanes_why(const mc_program* p) {
     if (const char* e = std::getenv("MC_EXPR_LANES"))  // 0: the tape (A/B, tests)
-        if (e[0] == '0') return false;
+        if (e[0] == '0') return "expression terms on the lanes are switched off (MC_EXPR_LANES=0)";
+    char buf[256];
+    bool grouped = false;
     for (const DevTerm& t : p->raw) {
         if (t.dist != MC_DIST_EXPR) continue;
-        if (t.primary >= 0 || t.npass != 1 || t.expr_n < 1) return false;
-        std::vector<int64_t> arrays;  // distinct data arrays (one LDS tile each)
-        for (int k = 0; k < t.expr_n; ++k) {
-            const DevExprNode& d = p->nodes[t.expr_base + k];
-            if (d.op != MC_EX_LEAF) continue;
-            if (d.prim) return false;
-            if (d.leaf.kind == MC_OP_DATA) {
-                if (std::find(arrays.begin(), arrays.end(), d.leaf.pool) == arrays.end())
-                    arrays.push_back(d.leaf.pool);
-            } else if (d.leaf.kind != MC_OP_CONST && d.leaf.kind != MC_OP_PSCALAR) {
-                return false;
-            }
+        std::vector<int32_t> vecs;
+        std::string why;
+        const int c = expr_term_class(p, t, &vecs, nullptr, &why);
+        if (c < 0)
+            return "expression terms other than data / broadcast parameter / constant leaves and "
+                   "parameter vectors gathered through one index (" + why + ") run on the "
+                   "chain-per-workgroup kernels (not sliceable)";
+        if (c == 1 && (int)vecs.size() > kLrMaxSlots) {
+            std::snprintf(buf, sizeof buf, "an expression term gathers %d parameter vectors: a "
+                          "bundle of more than %d private parameters per element does not fit a "
+                          "lane's register slots (not sliceable)", (int)vecs.size(), kLrMaxSlots);
+            return buf;
         }
-        if (arrays.empty() || (int)arrays.size() > kLrExprData) return false;
+        grouped |= c == 1;
     }
-    return true;
+    if (grouped) {
+        int64_t n = 0;
+        for (const DevTerm& t : p->raw) n += t.n;
+        if (n < kLrAutoMinElements) {
+            std::snprintf(buf, sizeof buf, "a gathered-parameter expression program of %lld "
+                          "elements (fewer than %lld) stays on the chain-per-workgroup kernels "
+                          "(not sliceable)", (long long)n, (long long)kLrAutoMinElements);
+            return buf;
+        }
+    }
+    return "";
 }
+inline bool expr_lanes_ok(const mc_program* p) { return expr_lanes_why(p).empty(); }
 // The term interpreter (k_hmc_sl) takes neither transformed operands, affine
 // locs nor expression terms: such sliced programs run on the lane-resident
 // kernels only (or, expression terms without the JIT, on the tape).

@@ -433,9 +433,34 @@ std::string flit(float v) {
 // A transformed broadcast parameter (LanePlan::shxf) is read through its
 // transform node only (the planner checks it): that node reads the lane's
 // transformed value sh.v and its adjoint is the value's cotangent.
+//   a grouped term (LanePlan::gx_off: parameter-vector / gather leaves, two
+//     chains): the sweep is a lambda over one bundle's run (its tile offset,
+//     length, the bundle's private values gq<off> of both chains and their
+//     adjoint sums ga<off>, summed over the run in element order as the
+//     broadcast leaves' p<k>), called once per first slot r0 of the lane with
+//     compile-time slot indices (lanes.h lr_slot_q / lr_slot_g_add).
+// elements interleaved per trip of a grouped term's run (two chains): 4, or 2
+// with MC_LANE_GROUP_INTERLEAVE=2 in the environment (A/B timing)
+int grp_interleave() {
+    const char* e = std::getenv("MC_LANE_GROUP_INTERLEAVE");
+    return (e && e[0] == '2') ? 2 : 4;
+}
+bool lane_term_grouped(const DevTerm& T, const LanePlan& L) {
+    for (int k = 0; k < T.expr_n; ++k)
+        if ((size_t)(T.expr_base + k) < L.gx_off.size() && L.gx_off[T.expr_base + k] >= 0)
+            return true;
+    return false;
+}
 void gen_lane_term(std::ostringstream& o, const DevTerm& T, const DevExprNode* N,
                    const LanePlan& L, bool one) {
     const int nn = T.expr_n;
+    const bool grp = lane_term_grouped(T, L);
+    auto goff = [&](int k) { return grp ? L.gx_off[T.expr_base + k] : -1; };
+    std::vector<int> goffs;  // the distinct slot offsets, ascending
+    for (int k = 0; k < nn; ++k)
+        if (goff(k) >= 0 && std::find(goffs.begin(), goffs.end(), goff(k)) == goffs.end())
+            goffs.push_back(goff(k));
+    std::sort(goffs.begin(), goffs.end());
     auto ordinal = [&](int poff) {
         for (int k = 0; k < L.Dsh; ++k)
             if (L.shl[k] == poff) return k;
@@ -447,13 +472,26 @@ void gen_lane_term(std::ostringstream& o, const DevTerm& T, const DevExprNode* N
         else x << "exf2{rl(sh." << f << ", " << 2 * K << "), rl(sh." << f << ", " << 2 * K + 1 << ")}";
         return x.str();
     };
+    if (grp && one)
+        o << "template <bool LP, bool G, int RS>\nMC_DEV void jit_lgo" << T.expr_base
+          << "(const MC_CONST LrTerm* T, const float* sd, int j, const float (&q)[RS],\n"
+          << "    float (&g)[RS], const LrShared& sh, float& lpp, float (&gsh)[kLrMaxShared]) {\n"
+          << "  const int32_t* lens = (const int32_t*)sd + T->len_off;\n"
+          << "  const int nslot = T->nslot;\n  (void)g;\n";
+    else if (grp)
+        o << "template <bool LP, int RS>\nMC_DEV void jit_lg" << T.expr_base
+          << "(const MC_CONST LrTerm* T, const float* sd, int j, LrPriv<RS>& R, const LrShared& sh,\n"
+          << "    float (&lpp)[2], float (&gshp)[kLrMaxShared][2]) {\n"
+          << "  const int32_t* lens = (const int32_t*)sd + T->len_off;\n"
+          << "  const int nslot = T->nslot;\n";
+    else
     o << (one ? "template <bool LP, bool G>\n" : "template <bool LP>\n")
       << "MC_DEV void jit_l" << (one ? "o" : "t") << T.expr_base
       << "(const MC_CONST LrTerm* T, const float* sd, int j, const LrShared& sh,\n"
       << (one ? "    float& lpp, float (&gsh)[kLrMaxShared]) {\n"
               : "    float (&lpp)[2], float (&gshp)[kLrMaxShared][2]) {\n")
-      << "  const int len = ((const int32_t*)sd)[T->len_off + j];\n"
-      << "  const exf2 wv = {T->weight, T->weight};\n"
+      << "  const int len = ((const int32_t*)sd)[T->len_off + j];\n";
+    o << "  const exf2 wv = {T->weight, T->weight};\n"
       << "  exf2 lpa = {0.0f, 0.0f}, lpt = {0.0f, 0.0f};\n  (void)lpa; (void)lpt;\n"
       << (one ? "  (void)gsh;\n" : "");
     auto xf_node = [&](int k) {
@@ -484,12 +522,13 @@ void gen_lane_term(std::ostringstream& o, const DevTerm& T, const DevExprNode* N
                   << "};\n";
             } else if (d.leaf.kind == MC_OP_PSCALAR) {
                 o << "  const exf2 v" << k << " = " << sh_read("q", ordinal(d.leaf.poff)) << ";\n";
-            } else {  // data: one tile per array (leaves of one array share it)
+            } else if (d.leaf.kind == MC_OP_DATA) {  // one tile per array (leaves of one array share it)
                 bool dup = false;
                 for (int r : dleaves) dup |= N[r].leaf.pool == d.leaf.pool;
                 if (!dup) {
-                    o << "  const float* d" << k << " = sd + T->eoff[" << dleaves.size()
-                      << "] + 4 * j;\n";
+                    if (!grp)  // (a grouped term: per run, below)
+                        o << "  const float* d" << k << " = sd + T->eoff[" << dleaves.size()
+                          << "] + 4 * j;\n";
                     dleaves.push_back(k);
                 }
             }
@@ -499,6 +538,18 @@ void gen_lane_term(std::ostringstream& o, const DevTerm& T, const DevExprNode* N
         if (part(k)) o << "  exf2 p" << k << " = {0.0f, 0.0f}, t" << k << " = {0.0f, 0.0f};\n";
     }
     o << "  const exf2 z2 = {0.0f, 0.0f};\n  (void)z2;\n";
+    if (grp) {  // one bundle's run
+        o << "  auto run = [&](const int toff, const int len";
+        for (int g : goffs) o << ", const exf2 gq" << g;
+        for (int g : goffs) o << ", exf2& ga" << g;
+        if (one)  // (the ragged tail's sums: component x only)
+            for (int g : goffs) o << ", exf2& gt" << g;
+        o << ") {\n";
+        for (size_t i = 0; i < dleaves.size(); ++i)
+            o << "  const float* d" << dleaves[i] << " = sd + T->eoff[" << i << "] + toff + 4 * j;\n";
+        for (int k = 0; k < nn; ++k)
+            if (goff(k) >= 0) o << "  const exf2 v" << k << " = gq" << goff(k) << ";\n";
+    }
     // E elements at once, their statements interleaved node by node (the
     // elements' dependency chains are independent, so the hazards of one —
     // transcendental results, packed read-after-write — are covered by the
@@ -546,6 +597,11 @@ void gen_lane_term(std::ostringstream& o, const DevTerm& T, const DevExprNode* N
         for (int e = 0; e < E; ++e) o << ind << nm('a', nn - 1, e) << " = wv;\n";
         for (int k = nn - 1; k >= 0; --k) {
             const DevExprNode& d = N[k];
+            if (goff(k) >= 0) {  // a gathered leaf: its bundle slot's adjoint sum
+                for (int e = 0; e < E; ++e)
+                    o << ind << (tail ? "gt" : "ga") << goff(k) << " += " << nm('a', k, e) << ";\n";
+                continue;
+            }
             if (d.op == MC_EX_LEAF && !raw_leaf(k)) continue;
             for (int e = 0; e < E; ++e) {
                 if (part(k)) {
@@ -569,7 +625,28 @@ void gen_lane_term(std::ostringstream& o, const DevTerm& T, const DevExprNode* N
     o << "  int u = 0;\n  for (; u + 4 <= len; u += 4) {\n";
     for (int k : dleaves)
         o << "    const float4 X" << k << " = *(const float4*)(d" << k << " + (u >> 2) * 256);\n";
-    {
+    if (grp && one) {  // two element pairs interleaved, as a chunk term's
+        std::vector<std::vector<std::string>> x(2);
+        for (int e = 0; e < 2; ++e)
+            for (int k : dleaves) {
+                const std::string X = "X" + std::to_string(k) + ".";
+                x[e].push_back("exf2{" + X + comp[2 * e] + ", " + X + comp[2 * e + 1] + "}");
+            }
+        emit(2, x, "    ", false);
+    } else if (grp) {  // kGrpInterleave elements at once, the trip's four in element order
+        const int kGrpInterleave = grp_interleave();
+        for (int h = 0; h < 4; h += kGrpInterleave) {
+            std::vector<std::vector<std::string>> x(kGrpInterleave);
+            for (int e = 0; e < kGrpInterleave; ++e)
+                for (int k : dleaves) {
+                    const std::string X = "X" + std::to_string(k) + ".";
+                    x[e].push_back("exf2{" + X + comp[h + e] + ", " + X + comp[h + e] + "}");
+                }
+            o << "    {\n";
+            emit(kGrpInterleave, x, "    ", false);
+            o << "    }\n";
+        }
+    } else {
         const int E = one ? 2 : 4;
         std::vector<std::vector<std::string>> x(E);
         for (int e = 0; e < E; ++e)
@@ -592,6 +669,32 @@ void gen_lane_term(std::ostringstream& o, const DevTerm& T, const DevExprNode* N
         emit(1, x, "    ", one);
     }
     o << "  }\n";
+    if (grp) {
+        // the lane's bundles, by first slot (unrolled: compile-time slot indices)
+        o << "  };\n";
+        for (int r0 = 0; r0 < kLrMaxSlots; ++r0) {
+            o << "  if constexpr (" << r0 << " < RS) {\n    const int len = " << r0
+              << " < nslot ? lens[" << r0 << " * 64 + j] : 0;\n    if (len > 0) {\n";
+            for (int g : goffs) o << "      exf2 ga" << g << " = {0.0f, 0.0f};\n";
+            if (one)
+                for (int g : goffs) o << "      exf2 gt" << g << " = {0.0f, 0.0f};\n";
+            o << "      run(T->toff[" << r0 << "], len";
+            for (int g : goffs)
+                o << (one ? ", lr_slot1_q<RS, " : ", lr_slot_q<RS, ") << r0 + g << (one ? ">(q)" : ">(R)");
+            for (int g : goffs) o << ", ga" << g;
+            if (one)
+                for (int g : goffs) o << ", gt" << g;
+            o << ");\n";
+            for (int g : goffs) {
+                if (one)
+                    o << "      if constexpr (G) lr_slot1_g_add<RS, " << r0 + g << ">(g, (ga" << g
+                      << ".x + ga" << g << ".y) + gt" << g << ".x);\n";
+                else
+                    o << "      lr_slot_g_add<RS, " << r0 + g << ">(R, ga" << g << ");\n";
+            }
+            o << "    }\n  }\n";
+        }
+    }
     if (one) {
         o << "  if constexpr (LP) lpp += (lpa.x + lpa.y) + lpt.x;\n  if constexpr (G) {\n";
         for (int k = 0; k < nn; ++k) {
@@ -617,15 +720,53 @@ void gen_lane_term(std::ostringstream& o, const DevTerm& T, const DevExprNode* N
 // per wave: k_hmc_lr; one: k_nuts_sl).
 std::string gen_lane_source(const mc_program* p) {
     std::ostringstream o;
+    bool any_grp = false;
+    for (const DevTerm& T : p->raw) any_grp |= T.dist == MC_DIST_EXPR && lane_term_grouped(T, p->lr);
     o << "// generated by jit.hip (lane-resident expression terms) for one program: do not edit\n"
-      << "#define MC_JIT_LANES 1\n#include \"mh_sliced.h\"\nnamespace mc {\n";
-    std::vector<int32_t> bases;
+      << "#define MC_JIT_LANES 1\n" << (any_grp ? "#define MC_JIT_LANES_GROUPED 1\n" : "")
+      << "#include \"mh_sliced.h\"\nnamespace mc {\n";
+    std::vector<int32_t> bases, gbases;  // chunk terms, grouped terms
     for (const DevTerm& T : p->raw) {
         if (T.dist != MC_DIST_EXPR) continue;
-        if (std::find(bases.begin(), bases.end(), T.expr_base) != bases.end()) continue;
+        if (std::find(bases.begin(), bases.end(), T.expr_base) != bases.end() ||
+            std::find(gbases.begin(), gbases.end(), T.expr_base) != gbases.end())
+            continue;
+        if (lane_term_grouped(T, p->lr)) {  // (the leaves as validated: host.h mc_program::rnodes)
+            gbases.push_back(T.expr_base);
+            gen_lane_term(o, T, p->rnodes.data() + T.expr_base, p->lr, false);
+            gen_lane_term(o, T, p->rnodes.data() + T.expr_base, p->lr, true);
+            continue;
+        }
         bases.push_back(T.expr_base);
         gen_lane_term(o, T, p->nodes.data() + T.expr_base, p->lr, false);
         gen_lane_term(o, T, p->nodes.data() + T.expr_base, p->lr, true);
+    }
+    if (any_grp) {
+        o << "template <int RS>\n"
+          << "MC_DEV void mc_jit_lane_gexpr(const MC_CONST LrTerm* T, const float* sd, int j,\n"
+          << "    LrPriv<RS>& R, const LrShared& sh, float (&lpp)[2],\n"
+          << "    float (&gshp)[kLrMaxShared][2], bool need_lp) {\n  switch (T->expr_base) {\n";
+        for (int32_t b : gbases)
+            o << "    case " << b << ":\n      if (need_lp) jit_lg" << b
+              << "<true, RS>(T, sd, j, R, sh, lpp, gshp);\n      else jit_lg" << b
+              << "<false, RS>(T, sd, j, R, sh, lpp, gshp);\n      break;\n";
+        o << "    default: break;\n  }\n}\n"
+          << "template <int RS>\n"
+          << "MC_DEV void mc_jit_lane_gexpr1(const MC_CONST LrTerm* T, const float* sd, int j,\n"
+          << "    const float (&q)[RS], float (&g)[RS], const LrShared& sh, float& lpp,\n"
+          << "    float (&gsh)[kLrMaxShared]) {\n  switch (T->expr_base) {\n";
+        for (int32_t b : gbases)
+            o << "    case " << b << ": jit_lgo" << b
+              << "<true, true, RS>(T, sd, j, q, g, sh, lpp, gsh); break;\n";
+        o << "    default: break;\n  }\n}\n"
+          << "template <int RS>\n"
+          << "MC_DEV void mc_jit_lane_gexpr1v(const MC_CONST LrTerm* T, const float* sd, int j,\n"
+          << "    const float (&q)[RS], const LrShared& sh, float& lpp) {\n"
+          << "  float g[RS], gsh[kLrMaxShared];\n  switch (T->expr_base) {\n";
+        for (int32_t b : gbases)
+            o << "    case " << b << ": jit_lgo" << b
+              << "<true, false, RS>(T, sd, j, q, g, sh, lpp, gsh); break;\n";
+        o << "    default: break;\n  }\n}\n";
     }
     o << "MC_DEV void mc_jit_lane_expr(const MC_CONST LrTerm* T, const float* sd, int j,\n"
       << "    const LrShared& sh, float (&lpp)[2], float (&gshp)[kLrMaxShared][2], bool need_lp) {\n"

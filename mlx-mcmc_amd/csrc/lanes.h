@@ -69,6 +69,13 @@ struct LrTerm {
     // a chunk term's value)
     int32_t expr_base, expr_n;
     int32_t eoff[kLrExprData];
+    // A grouped LS_EXPR term (parameter-vector / gather leaves through one
+    // element -> group map: alpha[g] + beta[g] * x) is marked by kb > 0, the
+    // number of distinct vectors it reads (an LS_EXPR term has no slope: kb is
+    // 0 on a chunk term).  The bundle of private parameters an element reads
+    // sits in consecutive slots of one lane; the term's runs, tiles (toff,
+    // lens, eoff) and lmin4 are indexed by the bundle's first slot, and the
+    // generated code holds each vector's slot offset (LanePlan::gx_off).
 };
 
 // Specialised term forms (Normal, broadcast scale, moment sums) with their
@@ -617,6 +624,50 @@ MC_DEV void mc_jit_lane_expr(const MC_CONST LrTerm* T, const float* sd, int j,
 // shared cotangent partials into gsh[K].
 MC_DEV void mc_jit_lane_expr1(const MC_CONST LrTerm* T, const float* sd, int j,
                               const LrShared& sh, float& lpp, float (&gsh)[kLrMaxShared]);
+#ifdef MC_JIT_LANES_GROUPED
+// A grouped LS_EXPR term (LrTerm::kb > 0; defined by the generated source of
+// a program that has one): per bundle of the lane (its first slot r0 < nslot)
+// the run of its elements, a gathered leaf at slot offset `off` reading
+// R.q[r0 + off] of both chains; its adjoint, summed over the run in element
+// order, completes R.g[r0 + off] inside the lane, as lr_affine_term's private
+// loc does.  Slot indices are compile-time (r0 + off >= RS: a dead branch).
+template <int RS>
+MC_DEV void mc_jit_lane_gexpr(const MC_CONST LrTerm* T, const float* sd, int j, LrPriv<RS>& R,
+                              const LrShared& sh, float (&lpp)[2],
+                              float (&gshp)[kLrMaxShared][2], bool need_lp);
+// slot S of the lane's private registers, both chains packed (S >= RS: unused)
+template <int RS, int S>
+MC_DEV f2 lr_slot_q(const LrPriv<RS>& R) {
+    if constexpr (S < RS) return (f2){R.q[S][0], R.q[S][1]};
+    else return (f2){0.0f, 0.0f};
+}
+template <int RS, int S>
+MC_DEV void lr_slot_g_add(LrPriv<RS>& R, f2 a) {
+    if constexpr (S < RS) {
+        R.g[S][0] += a[0];
+        R.g[S][1] += a[1];
+    }
+}
+// The same for one chain per wave (k_nuts_sl, k_mh_sl: the kernel's q[RS] and
+// g[RS]; two elements packed per instruction, the pairs' sums added at the
+// end), and its log p alone (reads q only).
+template <int RS>
+MC_DEV void mc_jit_lane_gexpr1(const MC_CONST LrTerm* T, const float* sd, int j,
+                               const float (&q)[RS], float (&g)[RS], const LrShared& sh,
+                               float& lpp, float (&gsh)[kLrMaxShared]);
+template <int RS>
+MC_DEV void mc_jit_lane_gexpr1v(const MC_CONST LrTerm* T, const float* sd, int j,
+                                const float (&q)[RS], const LrShared& sh, float& lpp);
+template <int RS, int S>
+MC_DEV f2 lr_slot1_q(const float (&q)[RS]) {
+    if constexpr (S < RS) return (f2){q[S], q[S]};
+    else return (f2){0.0f, 0.0f};
+}
+template <int RS, int S>
+MC_DEV void lr_slot1_g_add(float (&g)[RS], float a) {
+    if constexpr (S < RS) g[S] += a;
+}
+#endif
 // Its log p alone (k_mh_sl's forward pass).
 MC_DEV void mc_jit_lane_expr1v(const MC_CONST LrTerm* T, const float* sd, int j,
                                const LrShared& sh, float& lpp);
@@ -660,6 +711,12 @@ MC_DEV void lr_eval(const MC_CONST LrTerm* tt, int t0, int nact, const float* sd
                 continue;
             case LS_EXPR:
 #ifdef MC_JIT_LANES
+#ifdef MC_JIT_LANES_GROUPED
+                if (T->kb > 0) {
+                    mc_jit_lane_gexpr<RS>(T, sd, j, R, sh, lpp, gshp, need_lp);
+                    continue;
+                }
+#endif
                 mc_jit_lane_expr(T, sd, j, sh, lpp, gshp, need_lp);
 #endif
                 // (the library's own instantiations never see one: a program

@@ -266,7 +266,15 @@ k_mh_sl(LrCtx P, RunArgs A, float scale, int64_t chain_base, int64_t n_groups,
             shp.iv = is * is;
             shp.lg = lgv;
             for (int t = nsweep + ndirect; t < nact; ++t)
-                if (tt[t].sig == LS_EXPR) mc_jit_lane_expr1v(tt + t, sd, j, shp, lpp);
+                if (tt[t].sig == LS_EXPR) {
+#ifdef MC_JIT_LANES_GROUPED
+                    if (tt[t].kb > 0) {  // (a grouped term reads the proposal's privates)
+                        mc_jit_lane_gexpr1v<RS>(tt + t, sd, j, qn, shp, lpp);
+                        continue;
+                    }
+#endif
+                    mc_jit_lane_expr1v(tt + t, sd, j, shp, lpp);
+                }
         }
 #endif
         {  // the own prior of the lane's shared parameter, identity terms (slice 0)

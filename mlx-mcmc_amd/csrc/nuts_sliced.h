@@ -528,7 +528,16 @@ k_nuts_sl(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
                 float gxe[kLrMaxShared] = {0.0f, 0.0f, 0.0f, 0.0f};
                 if constexpr (!CF)
                     for (int t = nsweep + ndirect; t < nact; ++t)
-                        if (tt[t].sig == LS_EXPR) mc_jit_lane_expr1(tt + t, sd, j, sh, lpp, gxe);
+                        if (tt[t].sig == LS_EXPR) {
+#ifdef MC_JIT_LANES_GROUPED
+                            // (a grouped term: completes g[r] of the lane's bundles)
+                            if (tt[t].kb > 0) {
+                                mc_jit_lane_gexpr1<RS>(tt + t, sd, j, q, g, sh, lpp, gxe);
+                                continue;
+                            }
+#endif
+                            mc_jit_lane_expr1(tt + t, sd, j, sh, lpp, gxe);
+                        }
 #endif
                 if (rep > 1) {
 #pragma unroll

@@ -101,6 +101,18 @@ for sl, name in ((0, "lane-resident (auto)"), (1, "tape (num_slices=1)")):
     print(f"varying intercept G={G} N={N} {name}: {r / 1e6:.3f} M chain-steps/s "
           f"(kernel {prog.slice_kernel}, {prog.num_slices} slices; build {tb:.2f} s)")
     del cs, smp, prog
+# gathered parameter vectors inside the likelihood (grouped expression terms,
+# lanes.h LrTerm::kb): varying slopes alpha[g] + beta[g] * x and the
+# weighted/indexed model, on the lanes (automatic) and on the tape; few long
+# groups (weighted/indexed at G = 64) exceed a slice's LDS tile and stay on
+# the tape either way
+for gname, mk in (("varying slopes G=1000", lambda: W.varying_slopes(W.ns_product(), 1000, N)),
+                  ("weighted/indexed G=64", lambda: W.weighted_indexed(W.ns_product(), 64, N)),
+                  ("weighted/indexed G=1000", lambda: W.weighted_indexed(W.ns_product(), 1000, N))):
+    lpg, ig = mk()
+    for sl, nm in ((0, "auto"), (1, "tape, num_slices=1")):
+        r, tb, k = rate(lpg, ig, slices=sl, iters=20 if sl == 0 else 2)
+        print(f"{gname} N={N} ({nm}): {r / 1e6:.3f} M chain-steps/s (kernel {k}; build {tb:.2f} s)")
 lp, _ = W.two_predictor_regression(W.ns_product(), N)
 i2 = {"a": np.float32(0.5), "b1": np.float32(1.2), "b2": np.float32(-0.8),
       "log_sigma": np.float32(-0.5)}

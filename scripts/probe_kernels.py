@@ -26,6 +26,7 @@ MODELS = {
     "hierarchical": lambda: W.hierarchical(ns, 997, N),
     "hierarchical_reparam": lambda: W.hierarchical_reparam(ns, 997, N),
     "weighted_indexed": lambda: W.weighted_indexed(ns, 64, N),
+    "weighted_indexed_1000": lambda: W.weighted_indexed(ns, 1000, N),
     "tempered": lambda: W.tempered(ns, N),
     "cauchy": lambda: W.cauchy_location(ns, N),
     "gamma_beta": lambda: W.gamma_beta_regression(ns, N),
@@ -40,9 +41,10 @@ for name, mk in MODELS.items():
         mp = _trace.mh_program(prog)  # (kept alive while its handle is queried)
         mh = "sliced" if lib.mc_program_mh_sliced(mp.handle) == 1 else "tape"
         note = prog.kernel_note
+        # (lane_bundle > 0: gathered parameter vectors on the lanes, in bundles)
         print(f"{name:22s} terms {len(prog.model.terms):2d} affine {prog.model.n_affines} "
-              f"expr {prog.model.n_exprs}: HMC {hmc:10s} NUTS {nuts:7s} MH {mh:7s} {note[:70]}",
-              flush=True)
+              f"expr {prog.model.n_exprs}: HMC {hmc:10s} bundle {prog.lane_bundle} "
+              f"NUTS {nuts:7s} MH {mh:7s} {note[:70]}", flush=True)
     except Exception as e:  # noqa: BLE001
         print(f"{name:22s} error: {type(e).__name__}: {str(e)[:120]}", flush=True)
 
