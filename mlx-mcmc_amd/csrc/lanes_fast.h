@@ -183,10 +183,13 @@ MC_DEV void lf_moments(const float* xv, int len, int lmin4, int lmax, f2 th, f2&
     };
     const std::false_type acc;
     int u4 = 0;
-    // 16 elements per round; the next round's LDS loads are issued before
-    // this round's arithmetic (software pipelined over two register sets that
-    // alternate, so no copies: a lone wave per SIMD — fewer slices — does not
-    // wait for the load latency)
+    // 16 elements per round over two register sets that alternate (no
+    // copies), each round's loads written ahead of the round before it.  As
+    // compiled (scripts/isa_sweep.py, profiles/lf_sweep_pipeline/isa_parent.txt)
+    // only every second round's loads stay there: the register allocator
+    // gives set A's registers to round(B)'s temporaries, so A's loads are
+    // issued after round(B) and waited for at once.  lf_moments_pre pins the
+    // order; this form is kept where runs are a round or none long.
     if (lmin4 >= 4) {
         float4 A[4], B[4];
         auto load = [&](float4 (&X)[4], int g) {
@@ -224,6 +227,133 @@ MC_DEV void lf_moments(const float* xv, int len, int lmin4, int lmax, f2 th, f2&
                 if (!more_b) break;
             }
         }
+    } else {
+        a1[0] = a1[1] = a2[0] = a2[1] = (f2){0.f, 0.f};
+    }
+    // the groups every lane holds in full (uniform), then the ragged end:
+    // element e of the lanes with more elements (e < lmax, uniform bounds),
+    // masked per lane (the tile is padded to whole groups, so every load is
+    // in bounds); no exec-masked loop, no per-lane branch
+    for (; u4 < lmin4; ++u4) {
+        const float4 a = *(const float4*)(xv + u4 * 256);
+        pair((f2){a.x, a.y}, acc);
+        pair((f2){a.z, a.w}, acc);
+    }
+    const f2 z = {0.f, 0.f};
+    for (int e = 4 * lmin4; e < lmax; e += 4) {
+        const float4 a = *(const float4*)(xv + (e >> 2) * 256);
+        const float x[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (e + k >= lmax) break;  // (uniform)
+            f2 d = (f2){x[k], x[k]} - th;
+            d = (e + k < len) ? d : z;
+            a1[k & 1] += d;
+            a2[k & 1] = pk_fma(d, d, a2[k & 1]);
+        }
+    }
+    s1 = a1[0] + a1[1];
+    s2 = a2[0] + a2[1];
+}
+
+// The first two rounds' elements of a lane's run (lf_moments): register sets A
+// (groups 0-3) and B (groups 4-7, or the last full round's where there is
+// only one).  Their addresses depend on the run alone, not on the position,
+// so a step issues them ahead of the work that precedes its sweep
+// (lf_issue) and the sweep's first round finds them landed.
+struct LfPre {
+    float4 A[4], B[4];
+};
+
+MC_DEV void lf_load4(float4 (&X)[4], const float* xv, int g) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) X[q] = *(const float4*)(xv + (g + q) * 256);
+}
+
+// Issue the loads of LfPre.  Every lane loads, a lane without elements too
+// (its xv is in the tile); a run without a full round loads nothing.  The
+// scheduling barrier keeps the loads here: ahead of what the caller does next.
+template <bool REREAD = false>
+MC_DEV void lf_issue(const float* xv, int lmin4, LfPre& P) {
+    if constexpr (REREAD) asm volatile("" : "+s"(lmin4));
+    if (lmin4 >= 4) {
+        lf_load4(P.A, xv, 0);
+        lf_load4(P.B, xv, min(4, lmin4 - 4));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// lf_moments with the rounds' schedule pinned: the same sums in the same
+// order (the same bits).  P: the run's first two rounds, issued by lf_issue
+// (by the caller, as early as it can).
+//
+// The schedule as compiled (scripts/isa_sweep.py prints it;
+// profiles/lf_sweep_pipeline/isa_result.txt): a round is 16 elements, four
+// ds_read_b128 and 48 packed instructions.  A scheduling barrier after each
+// prefetch pins the order — loads of round k + 1, the 48 instructions of
+// round k, loads of round k + 2 ... — while the compiler still counts the
+// waits (lgkmcnt) itself: the wait for a set comes a whole round after its
+// issue, and round 0's a step's fixed work after it.
+template <bool REREAD = false>
+MC_DEV void lf_moments_pre(const float* xv, int len, int lmin4, int lmax, f2 th, LfPre& P, f2& s1,
+                           f2& s2) {
+    if constexpr (REREAD) asm volatile("" : "+s"(lmin4), "+s"(lmax));
+    f2 a1[2], a2[2];
+    // a register pair's elements broadcast by swizzle (op_sel on the pair,
+    // no copy of the odd register); the first pair assigns the accumulators
+    // (d and d * d: what 0 + d and fma(d, d, 0) round to), so no zeros are
+    // materialised per sweep
+    auto pair = [&](f2 xy, auto first) {
+        const f2 d0 = xy.xx - th;
+        const f2 d1 = lf_hi_minus(xy, th);
+        if constexpr (decltype(first)::value) {
+            a1[0] = d0;
+            a2[0] = d0 * d0;
+            a1[1] = d1;
+            a2[1] = d1 * d1;
+        } else {
+            a1[0] += d0;
+            a2[0] = pk_fma(d0, d0, a2[0]);
+            a1[1] += d1;
+            a2[1] = pk_fma(d1, d1, a2[1]);
+        }
+    };
+    const std::false_type acc;
+    int u4 = 0;
+    // 16 elements per round over two register sets that alternate (no copies).
+    // The trip count is derived once: nr full rounds; round 0 (set A) and
+    // round 1 (set B) are in flight on entry, a loop trip computes rounds
+    // k (B) and k + 1 (A) and prefetches rounds k + 1 and k + 2 — the second
+    // clamped to the last full round where the run has none (the loads are
+    // unconditional, so the sets never need copies) — and an odd last round
+    // is computed from set B without a prefetch.
+    if (lmin4 >= 4) {
+        float4(&A)[4] = P.A;
+        float4(&B)[4] = P.B;
+        auto round = [&](const float4 (&X)[4], auto first) {
+            pair((f2){X[0].x, X[0].y}, first);
+            pair((f2){X[0].z, X[0].w}, acc);
+#pragma unroll
+            for (int q = 1; q < 4; ++q) {
+                pair((f2){X[q].x, X[q].y}, acc);
+                pair((f2){X[q].z, X[q].w}, acc);
+            }
+        };
+        const int last = lmin4 - 4;
+        int n = (lmin4 >> 2) - 1;  // rounds after round 0
+        u4 = 4 * (n + 1);
+        round(A, std::true_type());
+        const float* xg = xv + 8 * 256;  // the next prefetch: round 2
+        for (; n >= 2; n -= 2) {
+            lf_load4(A, xg, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            round(B, acc);
+            lf_load4(B, n >= 3 ? xg + 4 * 256 : xv + last * 256, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            round(A, acc);
+            xg += 8 * 256;
+        }
+        if (n == 1) round(B, acc);
     } else {
         a1[0] = a1[1] = a2[0] = a2[1] = (f2){0.f, 0.f};
     }
@@ -522,11 +652,31 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
     // the swept terms' moment sums at the current point, both chains (a lane
     // without elements never writes its sums: they stay the zeros they are
     // declared with, so no zeros are materialised per sweep)
-    auto sweep = [&](f2 (&s1)[RS], f2 (&s2)[RS]) {
+    // PRE — one slot, a compile-time form and one lane per parameter compiled
+    // in (LFS_REP1: whole runs, several rounds a sweep; the Large shape): the
+    // step issues the sweep's first loads itself (sweep_issue, ahead of the
+    // work between two sweeps: 32 registers in flight over it, 206 -> 245
+    // VGPRs) and the rounds' order is pinned (lf_moments_pre).  Every other
+    // instantiation keeps lf_moments: split runs are a round or none long,
+    // and there the early loads and their scheduling barrier in the step cost
+    // more than they hid (same-box A/B: medium -1.4 %, small -4.1 %); the
+    // run-time form went past 256 registers with them, and with more slots
+    // the register sets went to scratch.
+    constexpr bool PRE = RS == 1 && CF && (SPEC & LFS_REP1) != 0;
+    auto sweep_issue = [&](LfPre& pre) {
+        if constexpr (PRE) lf_issue<true>(xv[0], lmin4[0], pre);
+    };
+    auto sweep = [&](f2 (&s1)[RS], f2 (&s2)[RS], LfPre& pre) {
 #pragma unroll
-        for (int r = 0; r < RS; ++r)
-            if (len[r] > 0)
-                lf_moments<RS == 1>(xv[r], len[r], lmin4[r], lmax[r], q[r], s1[r], s2[r]);
+        for (int r = 0; r < RS; ++r) {
+            if (len[r] > 0) {
+                if constexpr (PRE)
+                    lf_moments_pre<true>(xv[r], len[r], lmin4[r], lmax[r], q[r], pre, s1[r],
+                                         s2[r]);
+                else
+                    lf_moments<RS == 1>(xv[r], len[r], lmin4[r], lmax[r], q[r], s1[r], s2[r]);
+            }
+        }
     };
 
     const int L = cfg.num_leapfrog_steps;
@@ -707,9 +857,11 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
         f2 M1[RS], M2[RS];
 #pragma unroll
         for (int r = 0; r < RS; ++r) M1[r] = M2[r] = (f2){0.f, 0.f};
+        LfPre pre;
+        sweep_issue(pre);
         drift_private(false);
         drift_shared(false);
-        sweep(M1, M2);
+        sweep(M1, M2, pre);
         if (xchk && it == cfg.iter_begin) {  // (before the launch's first publish)
             const bool same = xcd_agree(xpoll, xslots, S, ebase + 1, ok);
             // (diagnostic: blocks found on one XCD / not, counted by slice 0,
@@ -854,6 +1006,9 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                 }
             }
             MC_STAMP(1);
+            // the next sweep's first loads (they do not depend on the position):
+            // in flight over the reduce-scatter, the publish and the drift
+            if constexpr (!LAST) sweep_issue(pre);
             // wave totals, reduce-scattered: pair P = 2 slot + chain
             float xr[2 * NRS];
             {
@@ -975,7 +1130,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             // A/B 83.2 vs 94.7 M steps/s, profiles/r4/ab)
             if constexpr (!LAST) {
                 drift_private(true);
-                sweep(M1, M2);
+                sweep(M1, M2, pre);
             }
             MC_STAMP(8);
             if (!X1) poll_issue();
