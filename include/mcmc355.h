@@ -503,6 +503,73 @@ int mc_nuts_run(const mc_program* prog, const mc_run_config* cfg,
                 void* state_dev, float* samples_dev, const mc_trace* trace,
                 void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- diagonal mass matrix (no reference counterpart: its README roadmap
+ * lists "Mass matrix adaptation") -------------------------------------------
+ * A per-chain metric M = diag(1 / minv) for HMC and NUTS on the
+ * chain-per-workgroup kernels k_hmc / k_nuts.  With msqrt_j = 1 / sqrt(minv_j),
+ * computed when minv_j is set (all f32, no FMA contraction):
+ *   momentum r_j = z_j * msqrt_j  (z_j the normal element j draws without a
+ *   metric), velocity v_j = minv_j * r_j, kinetic energy 0.5 sum r_j v_j, drift
+ *   q_j += e * v_j; kicks, accept rule, slice and the U-turn test (on the
+ *   momentum r) as without a metric.  minv = 1 reproduces mc_hmc_run /
+ *   mc_nuts_run on those kernels bit for bit.
+ * Adaptation (adapt != 0, warmup iterations only; Stan's windows, per chain,
+ * never pooled): with W = num_warmup, init = 75, term = 50, base = 25, or
+ * init = floor(0.15 W), term = floor(0.1 W), base = W - init - term when
+ * init + term + base > W; nothing is adapted when W < 20.  Windows tile
+ * [init, W - term): the first has base iterations, each next twice the one
+ * before, and a window is stretched to W - term when the one after it would
+ * not fit.  After every iteration of a window the chain's position enters a
+ * Welford accumulator (f32); at the window's last iteration, with n draws,
+ *   minv_j = (n / (n + 5)) * M2_j / (n - 1) + 1e-3 * (5 / (n + 5))
+ * (a value that is not finite or not positive keeps the old one), msqrt is
+ * recomputed and the accumulator reset.  NUTS then restarts dual averaging
+ * (mu = f32 log(10 * eps), H_bar = 0, eps_bar = 1, its iteration counter m
+ * counts from the restart); HMC keeps its x0.95 / x1.05 rule.
+ *
+ * The metric lives in its own device buffer of mc_metric_bytes() bytes, the
+ * state blob is unchanged:
+ *   [mc_metric_scalars x C][pad to 256 B][minv C x D f32][pad][msqrt][pad]
+ *   [mean][pad][M2]
+ * (mc_metric_offsets gives the byte offsets of the four sections).  The
+ * adaptation state persists in it, so a run may be cut into launches anywhere
+ * and chains may be split over launches and devices without changing a bit. */
+typedef struct mc_metric_scalars {
+    int32_t n_window;   /* draws in the window's accumulator                 */
+    int32_t n_updates;  /* metric updates so far                            */
+    int64_t da_origin;  /* NUTS: iteration of the last dual-averaging restart */
+} mc_metric_scalars;
+
+/* The window ends (exclusive; the metric is updated after iteration end - 1)
+ * for num_warmup warmup iterations: writes the first min(count, cap) into
+ * ends (may be NULL) and returns the count.  Host only.                     */
+int32_t mc_metric_schedule(int64_t num_warmup, int64_t* ends, int32_t cap);
+int64_t mc_metric_bytes(const mc_program* prog, int64_t num_chains);
+int mc_metric_offsets(const mc_program* prog, int64_t num_chains, int64_t* minv_offset,
+                      int64_t* msqrt_offset, int64_t* mean_offset, int64_t* m2_offset);
+/* Fill the metric buffer: minv from inv_mass_dev ([C, D] f32, or one [D]
+ * vector for every chain when bcast = 1, or ones when NULL), msqrt from it,
+ * accumulator and scalars zero.  An entry that is not finite or not positive
+ * is MC_ERR_INVALID.  Not a launch function: the values are validated on the
+ * host, so it synchronises the stream.  (For a program built under
+ * mc_debug_program_host_only both pointers are host memory: the validation
+ * and the layout can be checked without a device.)                         */
+int mc_metric_init(const mc_program* prog, int64_t num_chains, const float* inv_mass_dev,
+                   int32_t bcast, void* metric_dev, void* hip_stream);
+/* mc_hmc_run / mc_nuts_run with the metric of metric_dev (same workspace
+ * sizes); adapt != 0 adapts it during the warmup iterations of the launch.
+ * MC_ERR_UNSUPPORTED for a program whose launches would not go to k_hmc /
+ * k_nuts (a sliced or lane-resident plan: build the program with
+ * mc_program_set_slices(prog, 1)).  Asynchronous, no allocation.           */
+int mc_hmc_run_metric(const mc_program* prog, const mc_run_config* cfg,
+                      void* state_dev, float* samples_dev, const mc_trace* trace,
+                      void* workspace_dev, int64_t workspace_bytes, void* metric_dev,
+                      int32_t adapt, void* hip_stream);
+int mc_nuts_run_metric(const mc_program* prog, const mc_run_config* cfg,
+                       void* state_dev, float* samples_dev, const mc_trace* trace,
+                       void* workspace_dev, int64_t workspace_bytes, void* metric_dev,
+                       int32_t adapt, void* hip_stream);
+
 /* Random-walk Metropolis-Hastings (metropolis.py:6-101): per iteration
  * q' = q + f32(z * f32(proposal_scale)), z ~ N(0, I) (Philox, tag
  * MC_RNG_TAG_PROPOSAL), accept iff f32 log U < f32(lp(q') - lp(q)) (NaN

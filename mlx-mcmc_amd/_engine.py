@@ -84,6 +84,7 @@ class ChainSet:
                                           self.step_size0, _lib.ptr(self.state),
                                           _lib.stream_handle()))
         self._ws = None
+        self.metric = None
 
     # -- views ---------------------------------------------------------------
     def positions(self):
@@ -101,6 +102,45 @@ class ChainSet:
         n = self.C * SCALARS_DTYPE.itemsize
         raw = self.state[:n].cpu().numpy()
         return np.frombuffer(raw.tobytes(), dtype=SCALARS_DTYPE).copy()
+
+    # -- diagonal metric (csrc/metric.h) ----------------------------------------
+    def set_metric(self, inverse_mass=None) -> None:
+        """Allocate the metric buffer and fill it (mc_metric_init): ``inverse_mass``
+        is None (ones), one [D] vector for every chain or [C, D]; a non-finite or
+        non-positive entry raises EngineError(MC_ERR_INVALID).  ``run_hmc_metric``
+        / ``run_nuts_metric`` then run with it."""
+        import torch
+
+        nbytes = self.lib.mc_metric_bytes(self.program.handle, self.C)
+        offs = [ctypes.c_int64() for _ in range(4)]
+        _lib.check(self.lib.mc_metric_offsets(self.program.handle, self.C,
+                                              *[ctypes.byref(o) for o in offs]))
+        self._metric_off = dict(zip(("minv", "msqrt", "mean", "m2"), (o.value for o in offs)))
+        src, bcast = None, 0
+        if inverse_mass is not None:
+            a = np.ascontiguousarray(inverse_mass, np.float32)
+            if a.shape not in ((self.D,), (self.C, self.D)):
+                raise ValueError(f"inverse mass must be [{self.D}] or [{self.C}, {self.D}], "
+                                 f"not {list(a.shape)}")
+            bcast = 1 if a.ndim == 1 else 0
+            src = torch.as_tensor(a).to(self.device)
+        metric = torch.zeros(int(nbytes), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.mc_metric_init(self.program.handle, self.C, _lib.ptr(src), bcast,
+                                           _lib.ptr(metric), _lib.stream_handle()))
+        self.metric = metric
+
+    def _metric_section(self, name: str):
+        o, n = self._metric_off[name], self.C * self.D
+        return self.metric[o:o + 4 * n].view(torch_float32()).view(self.C, self.D)
+
+    def inverse_mass(self):
+        """[C, D] float32 view of the metric's minv (device)."""
+        return self._metric_section("minv")
+
+    def metric_scalars(self) -> np.ndarray:
+        dt = np.dtype(_lib.McMetricScalars)
+        raw = self.metric[:self.C * dt.itemsize].cpu().numpy()
+        return np.frombuffer(raw.tobytes(), dtype=dt).copy()
 
     # -- launches ------------------------------------------------------------
     def _workspace(self, nbytes: int):
@@ -158,6 +198,22 @@ class ChainSet:
             ctypes.byref(tr) if tr is not None else None, _lib.ptr(ws),
             ws.numel() if ws is not None else 0, _lib.stream_handle()))
 
+    def run_hmc_metric(self, *, adapt: bool = False, samples=None,
+                       trace: Optional[Trace] = None, **cfg):
+        """``run_hmc`` with the metric of ``set_metric`` (mc_hmc_run_metric);
+        ``adapt`` adapts it during the launch's warmup iterations."""
+        if self.metric is None:
+            self.set_metric()
+        c = self._config(**cfg)
+        need = self.lib.mc_hmc_workspace_bytes(self.program.handle, self.C)
+        ws = self._workspace(need)
+        tr = trace.c_struct() if trace is not None else None
+        _lib.check(self.lib.mc_hmc_run_metric(
+            self.program.handle, ctypes.byref(c), _lib.ptr(self.state), _lib.ptr(samples),
+            ctypes.byref(tr) if tr is not None else None, _lib.ptr(ws),
+            ws.numel() if ws is not None else 0, _lib.ptr(self.metric), 1 if adapt else 0,
+            _lib.stream_handle()))
+
     def run_mh(self, *, proposal_scale: float, samples=None, trace: Optional[Trace] = None,
                **cfg):
         """Random-walk Metropolis-Hastings iterations (csrc/mh.h)."""
@@ -194,6 +250,24 @@ class ChainSet:
             self.program.handle, ctypes.byref(c), _lib.ptr(self.state), _lib.ptr(samples),
             ctypes.byref(tr) if tr is not None else None, _lib.ptr(ws),
             ws.numel() if ws is not None else 0, _lib.stream_handle()))
+
+    def run_nuts_metric(self, *, adapt: bool = False, samples=None,
+                        trace: Optional[Trace] = None, **cfg):
+        """``run_nuts`` with the metric of ``set_metric`` (mc_nuts_run_metric)."""
+        if self.metric is None:
+            self.set_metric()
+        c = self._config(**cfg)
+        need = self.lib.mc_nuts_workspace_bytes(self.program.handle, self.C, c.max_tree_depth)
+        if need < 0:
+            raise _lib.EngineError(_lib.MC_ERR_UNSUPPORTED,
+                                   f"max_tree_depth {c.max_tree_depth} not supported")
+        ws = self._workspace(need)
+        tr = trace.c_struct() if trace is not None else None
+        _lib.check(self.lib.mc_nuts_run_metric(
+            self.program.handle, ctypes.byref(c), _lib.ptr(self.state), _lib.ptr(samples),
+            ctypes.byref(tr) if tr is not None else None, _lib.ptr(ws),
+            ws.numel() if ws is not None else 0, _lib.ptr(self.metric), 1 if adapt else 0,
+            _lib.stream_handle()))
 
 
 def torch_float32():

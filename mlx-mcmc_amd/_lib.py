@@ -142,6 +142,14 @@ class McChainScalars(ctypes.Structure):
     ]
 
 
+class McMetricScalars(ctypes.Structure):
+    _fields_ = [
+        ("n_window", ctypes.c_int32),
+        ("n_updates", ctypes.c_int32),
+        ("da_origin", ctypes.c_int64),
+    ]
+
+
 class McRunConfig(ctypes.Structure):
     _fields_ = [
         ("num_chains", ctypes.c_int64),
@@ -240,6 +248,18 @@ SIGNATURES = [
     ("mc_nuts_run", ctypes.c_int,
      [_VP, ctypes.POINTER(McRunConfig), _VP, _VP, ctypes.POINTER(McTrace), _VP,
       ctypes.c_int64, _VP]),
+    ("mc_metric_schedule", ctypes.c_int32,
+     [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]),
+    ("mc_metric_bytes", ctypes.c_int64, [_VP, ctypes.c_int64]),
+    ("mc_metric_offsets", ctypes.c_int,
+     [_VP, ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int64)] * 4),
+    ("mc_metric_init", ctypes.c_int, [_VP, ctypes.c_int64, _VP, ctypes.c_int32, _VP, _VP]),
+    ("mc_hmc_run_metric", ctypes.c_int,
+     [_VP, ctypes.POINTER(McRunConfig), _VP, _VP, ctypes.POINTER(McTrace), _VP,
+      ctypes.c_int64, _VP, ctypes.c_int32, _VP]),
+    ("mc_nuts_run_metric", ctypes.c_int,
+     [_VP, ctypes.POINTER(McRunConfig), _VP, _VP, ctypes.POINTER(McTrace), _VP,
+      ctypes.c_int64, _VP, ctypes.c_int32, _VP]),
     ("mc_mh_workspace_bytes", ctypes.c_int64, [_VP, ctypes.c_int64]),
     ("mc_mh_run", ctypes.c_int,
      [_VP, ctypes.POINTER(McRunConfig), ctypes.c_double, _VP, _VP, ctypes.POINTER(McTrace), _VP,

@@ -2191,6 +2191,7 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
     p->h_data = dpool;
     p->h_index = ipool;
     if (g_program_host_only) {  // test hook: the host tables only (no device)
+        p->host_only = true;
         *out = p;
         return MC_OK;
     }
@@ -2443,6 +2444,77 @@ extern "C" int mc_state_init(const mc_program* p, int64_t C, const float* q0, do
         default: return p->ex ? launch_init<8, true>(p, C, q0, eps0, state, st)
                               : launch_init<8, false>(p, C, q0, eps0, state, st);
     }
+}
+
+// ---------------------------------------------------------------------------
+// diagonal metric buffer (metric.h)
+// ---------------------------------------------------------------------------
+extern "C" int32_t mc_metric_schedule(int64_t W, int64_t* ends, int32_t cap) {
+    const MetricSchedule s = metric_schedule(W);
+    int32_t n = 0;
+    for (int64_t it = s.init; metric_slow_phase(s, W, it);) {
+        const int64_t end = metric_window_end(s, W, it);
+        if (ends && n < cap) ends[n] = end;
+        ++n;
+        it = end;
+    }
+    return n;
+}
+
+extern "C" int64_t mc_metric_bytes(const mc_program* p, int64_t C) {
+    if (!p || C < 0) return -1;
+    return metric_layout(p, C).total;
+}
+
+extern "C" int mc_metric_offsets(const mc_program* p, int64_t C, int64_t* minv_off,
+                                 int64_t* msqrt_off, int64_t* mean_off, int64_t* m2_off) {
+    if (!p || C < 0) return fail(MC_ERR_INVALID, "bad arguments");
+    const MetricLayout L = metric_layout(p, C);
+    if (minv_off) *minv_off = L.minv;
+    if (msqrt_off) *msqrt_off = L.msqrt;
+    if (mean_off) *mean_off = L.mean;
+    if (m2_off) *m2_off = L.m2;
+    return MC_OK;
+}
+
+extern "C" int mc_metric_init(const mc_program* p, int64_t C, const float* inv_mass, int32_t bcast,
+                              void* metric, void* stream) {
+    if (!p || C < 0 || (C > 0 && !metric)) return fail(MC_ERR_INVALID, "bad arguments");
+    if (C == 0) return MC_OK;
+    const int64_t D = p->D;
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<float> in;
+    if (inv_mass) {
+        in.resize((size_t)((bcast ? 1 : C) * D));
+        if (p->host_only) {
+            std::memcpy(in.data(), inv_mass, in.size() * 4);
+        } else {
+            MC_HIP_TRY(hipMemcpyAsync(in.data(), inv_mass, in.size() * 4, hipMemcpyDeviceToHost, st));
+            MC_HIP_TRY(hipStreamSynchronize(st));
+        }
+        for (size_t i = 0; i < in.size(); ++i)
+            if (!(in[i] > 0.0f) || !std::isfinite(in[i]))
+                return fail(MC_ERR_INVALID, "inverse mass entry %lld (chain %lld, element %lld) is "
+                            "%g: every entry must be finite and positive", (long long)i,
+                            (long long)(i / (size_t)D), (long long)(i % (size_t)D), (double)in[i]);
+    }
+    const MetricLayout L = metric_layout(p, C);
+    std::vector<char> buf((size_t)L.total, 0);  // scalars and accumulator zero
+    float* minv = (float*)(buf.data() + L.minv);
+    float* msqrt = (float*)(buf.data() + L.msqrt);
+    for (int64_t c = 0; c < C; ++c)
+        for (int64_t j = 0; j < D; ++j) {
+            const float v = inv_mass ? in[(size_t)((bcast ? 0 : c * D) + j)] : 1.0f;
+            minv[c * D + j] = v;
+            msqrt[c * D + j] = 1.0f / std::sqrt(v);
+        }
+    if (p->host_only) {
+        std::memcpy(metric, buf.data(), buf.size());
+    } else {
+        MC_HIP_TRY(hipMemcpyAsync(metric, buf.data(), buf.size(), hipMemcpyHostToDevice, st));
+        MC_HIP_TRY(hipStreamSynchronize(st));
+    }
+    return MC_OK;
 }
 
 

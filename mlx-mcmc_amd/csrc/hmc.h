@@ -15,16 +15,25 @@
 // proposal's log density / gradient are carried over, so an iteration costs
 // L gradient evaluations instead of 2L + 2.  The arithmetic of every value
 // is unchanged (two separate half kicks, no FMA contraction).
+//
+// MET (off by default; the instantiations without it are unchanged): a
+// per-chain diagonal metric (metric.h), passed as one trailing MetricDev
+// argument: momentum z * msqrt, drift and kinetic energy through the velocity
+// minv * p, and during warmup the windowed adaptation of minv.  minv and msqrt
+// sit in LDS after the arena when the launch found room (MetricDev::in_lds),
+// else they are read from the metric buffer.
 #pragma once
 #include "eval.h"
+#include "metric.h"
 #include "philox.h"
 
 namespace mc {
 
-template <int WPC, bool LDS_ARENA, bool EX>
+template <int WPC, bool LDS_ARENA, bool EX, bool MET = false, typename... MArg>
 __global__ void __launch_bounds__(WPC >= 4 ? 64 * WPC : 256)
 k_hmc(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, float* samples,
-      TraceDev tr, float* ws) {
+      TraceDev tr, float* ws, MArg... met) {
+    static_assert(sizeof...(MArg) == (MET ? 1 : 0), "MET takes one MetricDev argument");
     constexpr int CPB = (WPC >= 4) ? 1 : 4 / WPC;
     constexpr int T = 64 * WPC;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -46,6 +55,21 @@ k_hmc(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, flo
     float* qB = arena + 2 * Dp;
     float* gB = arena + 3 * Dp;
     float* p = arena + 4 * Dp;
+    const MetricDev M = metric_arg<MET>(met...);
+    float* mnv = nullptr;
+    float* msq = nullptr;
+    MetricScalars ms = {};
+    if constexpr (MET) {
+        const bool ml = LDS_ARENA && M.in_lds;
+        mnv = ml ? arena + 5 * Dp : M.minv + c * D;
+        msq = ml ? arena + 6 * Dp : M.msqrt + c * D;
+        if (ml)
+            for (int j = G.tid; j < D; j += T) {
+                mnv[j] = M.minv[c * D + j];
+                msq[j] = M.msqrt[c * D + j];
+            }
+        ms = M.sc[c];
+    }
 
     MC_STAMP_INIT
     float lp = scal[c].logp;
@@ -85,8 +109,14 @@ k_hmc(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, flo
             for (int k = 0; k < 4; ++k) {
                 const int j = 4 * m + k;
                 if (j < D) {
-                    p[j] = z[k];
-                    kp += z[k] * z[k];
+                    if constexpr (MET) {
+                        const float rj = z[k] * msq[j];
+                        p[j] = rj;
+                        kp += rj * (mnv[j] * rj);
+                    } else {
+                        p[j] = z[k];
+                        kp += z[k] * z[k];
+                    }
                 }
             }
         }
@@ -104,7 +134,10 @@ k_hmc(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, flo
                 if (l > 0) pj = pj + h * gj;  // second half kick of step l-1
                 pj = pj + h * gj;             // first half kick of step l
                 p[j] = pj;
-                qB[j] = cq[j] + e * pj;
+                if constexpr (MET)
+                    qB[j] = cq[j] + e * (mnv[j] * pj);
+                else
+                    qB[j] = cq[j] + e * pj;
                 gB[j] = 0.0f;  // the evaluator accumulates into a zeroed gradient
             }
             G.sync();
@@ -117,7 +150,10 @@ k_hmc(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, flo
         float kp1 = 0.0f;
         for (int j = G.tid; j < D; j += T) {
             const float pj = (L > 0) ? p[j] + h * cg[j] : p[j];
-            kp1 += pj * pj;
+            if constexpr (MET)
+                kp1 += pj * (mnv[j] * pj);
+            else
+                kp1 += pj * pj;
         }
         const float H1 = -lpn + 0.5f * G.sum(kp1);
         const float ratio = -(H1 - H0);
@@ -155,6 +191,9 @@ k_hmc(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, flo
                 if (tr.n_leapfrog) tr.n_leapfrog[o] = L;
             }
         }
+        if constexpr (MET)
+            if (warm && M.adapt)
+                metric_adapt<T>(M, ms, c, D, cfg.num_warmup, it, qA, mnv, msq, G.tid);
         G.sync();
     }
 
@@ -172,6 +211,7 @@ k_hmc(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, flo
         sc.warmup_accept = warm_acc;
         sc.warmup_total = warm_tot;
         sc.n_grad += cfg.iter_count * (int64_t)L;
+        if constexpr (MET) M.sc[c] = ms;
     }
 }
 

@@ -132,6 +132,7 @@ struct mc_program {
                                       // term's leaves are sorted and tiled for the tape
                                       // (original pools, element order): the planners' input
     bool ex = false;                 // has expression terms: the EX kernel instantiations
+    bool host_only = false;          // built under mc_debug_program_host_only: no device tables
     DevExprNode* d_nodes = nullptr;
     float* d_data = nullptr;
     int32_t* d_index = nullptr;
@@ -445,6 +446,38 @@ inline int dispatch_tape(const mc_program* p, bool lds, F&& f) {
         default: return arena(std::integral_constant<int, 8>{});
     }
 }
+// ---------------------------------------------------------------------------
+// diagonal metric (metric.h): buffer layout and the MET kernels' argument
+// ---------------------------------------------------------------------------
+struct MetricLayout {
+    int64_t minv, msqrt, mean, m2, total;  // byte offsets of the [C, D] sections, size
+};
+inline MetricLayout metric_layout(const mc_program* p, int64_t C) {
+    auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
+    const int64_t sec = al(C * p->D * 4);
+    MetricLayout L;
+    L.minv = al(C * (int64_t)sizeof(mc_metric_scalars));
+    L.msqrt = L.minv + sec;
+    L.mean = L.msqrt + sec;
+    L.m2 = L.mean + sec;
+    L.total = L.m2 + sec;
+    return L;
+}
+inline MetricDev metricdev_of(const mc_program* p, int64_t C, void* metric, int adapt,
+                              bool in_lds) {
+    const MetricLayout L = metric_layout(p, C);
+    char* b = (char*)metric;
+    MetricDev M;
+    M.sc = (mc_metric_scalars*)b;
+    M.minv = (float*)(b + L.minv);
+    M.msqrt = (float*)(b + L.msqrt);
+    M.mean = (float*)(b + L.mean);
+    M.m2 = (float*)(b + L.m2);
+    M.adapt = adapt ? 1 : 0;
+    M.in_lds = in_lds ? 1 : 0;
+    return M;
+}
+
 // ---------------------------------------------------------------------------
 // HMC / NUTS launches
 // ---------------------------------------------------------------------------

@@ -32,6 +32,7 @@
 // and the H0 recomputation at every leaf are cost-only).
 #pragma once
 #include "eval.h"
+#include "metric.h"
 #include "philox.h"
 
 namespace mc {
@@ -71,10 +72,17 @@ MC_DEV int ctz_u32(uint32_t x) { return __builtin_ctz(x); }
 // LDS_ARENA: the arena lives in the workgroup's LDS after the group scratch
 // and the pending words (every trajectory vector one LDS round trip away
 // instead of an L2 one); else in the global workspace.
-template <int WPC, bool LDS_ARENA, bool EX>
+// MET (off by default; the instantiations without it are unchanged): a
+// per-chain diagonal metric (metric.h), passed as one trailing MetricDev
+// argument: momentum z * msqrt, the leaf's drift and kinetic energy through the
+// velocity minv * r, the U-turn test on the momentum as it is; during warmup
+// the windowed adaptation of minv, and at each update dual averaging restarts
+// (mu = f32 log(10 eps), H_bar = 0, eps_bar = 1, m counted from there).
+template <int WPC, bool LDS_ARENA, bool EX, bool MET = false, typename... MArg>
 __global__ void __launch_bounds__(WPC >= 4 ? 64 * WPC : 256)
 k_nuts(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, float* samples,
-       TraceDev tr, float* ws) {
+       TraceDev tr, float* ws, MArg... met) {
+    static_assert(sizeof...(MArg) == (MET ? 1 : 0), "MET takes one MetricDev argument");
     constexpr int CPB = (WPC >= 4) ? 1 : 4 / WPC;
     constexpr int T = 64 * WPC;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -118,6 +126,23 @@ k_nuts(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, fl
     float* pool = first + 2 * (int64_t)(MAXJ + 1) * Dp;  // slot s: q at 2s, g at 2s+1
     float* sq = st_q + c * D;  // current sample (theta0 of the next iteration)
     float* sg = st_g + c * D;
+    const MetricDev M = metric_arg<MET>(met...);
+    float* mnv = nullptr;
+    float* msq = nullptr;
+    MetricScalars ms = {};
+    if constexpr (MET) {
+        const bool ml = LDS_ARENA && M.in_lds;
+        mnv = ml ? ar + nuts_arena_vectors(MAXJ) * Dp : M.minv + c * D;
+        msq = ml ? mnv + Dp : M.msqrt + c * D;
+        if (ml) {
+            for (int j = G.tid; j < D; j += T) {
+                mnv[j] = M.minv[c * D + j];
+                msq[j] = M.msqrt[c * D + j];
+            }
+            G.sync();  // read by the Philox-block mapping of the momentum draw
+        }
+        ms = M.sc[c];
+    }
 
     MC_STAMP_INIT
     mc_chain_scalars sc = scal[c];
@@ -153,8 +178,14 @@ k_nuts(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, fl
             for (int k = 0; k < 4; ++k) {
                 const int j = 4 * m + k;
                 if (j < D) {
-                    Mr[j] = z[k];
-                    kp += z[k] * z[k];
+                    if constexpr (MET) {
+                        const float rj = z[k] * msq[j];
+                        Mr[j] = rj;
+                        kp += rj * (mnv[j] * rj);
+                    } else {
+                        Mr[j] = z[k];
+                        kp += z[k] * z[k];
+                    }
                 }
             }
         }
@@ -218,7 +249,10 @@ k_nuts(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, fl
                 for (int jj = G.tid; jj < D; jj += T) {
                     const float pj = Er[jj] + h * Eg[jj];
                     Er[jj] = pj;
-                    Eq[jj] = Eq[jj] + e * pj;
+                    if constexpr (MET)
+                        Eq[jj] = Eq[jj] + e * (mnv[jj] * pj);
+                    else
+                        Eq[jj] = Eq[jj] + e * pj;
                     Eg[jj] = 0.0f;  // the evaluator accumulates into a zeroed gradient
                 }
                 G.sync();
@@ -229,7 +263,10 @@ k_nuts(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, fl
                 for (int jj = G.tid; jj < D; jj += T) {
                     const float pj = Er[jj] + h * Eg[jj];
                     Er[jj] = pj;
-                    kl += pj * pj;
+                    if constexpr (MET)
+                        kl += pj * (mnv[jj] * pj);
+                    else
+                        kl += pj * pj;
                 }
                 const float Hl = -lpl + 0.5f * G.sum(kl);
                 ++leaves;
@@ -347,7 +384,8 @@ k_nuts(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, fl
         sc.n_total += 1;
         sc.depth_sum += j;
         if (warm && cfg.adapt_step_size) {  // dual averaging, nuts.py:299-310
-            const double m = (double)it;
+            double m = (double)it;
+            if constexpr (MET) m = (double)(it - ms.da_origin);
             const double eta = 1.0 / (m + 10.0);
             sc.h_bar = (1.0 - eta) * sc.h_bar + eta * (cfg.target_accept - alpha);
             const float lf = sc.mu - (float)(sqrt(m + 1.0) / 0.05 * sc.h_bar);
@@ -358,6 +396,16 @@ k_nuts(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, fl
             const double m_eta = pow(m + 1.0, -0.75);
             const double lb = m_eta * log(eps) + (1.0 - m_eta) * log(sc.step_size_bar);
             sc.step_size_bar = (double)mc_expf_ref((float)lb);
+        }
+        if constexpr (MET) {
+            if (warm && M.adapt &&
+                metric_adapt<T>(M, ms, c, D, cfg.num_warmup, it, sq, mnv, msq, G.tid) &&
+                cfg.adapt_step_size) {
+                sc.mu = mc_logf_ref((float)(10.0 * eps));
+                sc.h_bar = 0.0;
+                sc.step_size_bar = 1.0;
+                ms.da_origin = it + 1;
+            }
         }
         if (!warm && samples != nullptr) {
             const int64_t si = it - cfg.num_warmup - cfg.sample_begin;
@@ -388,6 +436,7 @@ k_nuts(DevCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, fl
         sc.step_size = eps;
         sc.n_grad += n_grad;
         scal[c] = sc;
+        if constexpr (MET) M.sc[c] = ms;
     }
 }
 

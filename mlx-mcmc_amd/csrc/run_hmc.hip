@@ -158,9 +158,13 @@ extern "C" int64_t mc_hmc_workspace_bytes(const mc_program* p, int64_t C) {
     return std::max(x, C * 5 * (int64_t)dpad_of(p->D) * 4);
 }
 
-template <int WPC, bool LDS, bool EX>
+// MET: the metric instantiation (metric.h) on the buffer `metric`; minv and
+// msqrt join the arena in LDS when the two extra vectors still fit its budget
+// (the arena decision itself, and so the workspace, is the one without a metric)
+template <int WPC, bool LDS, bool EX, bool MET = false>
 static int launch_hmc(const mc_program* p, const mc_run_config* cfg, void* state,
-                      float* samples, const mc_trace* tr, float* ws, hipStream_t st) {
+                      float* samples, const mc_trace* tr, float* ws, hipStream_t st,
+                      void* metric = nullptr, int adapt = 0) {
     int64_t qo, go;
     mc_state_offsets(p, cfg->num_chains, &qo, &go);
     char* b = (char*)state;
@@ -170,6 +174,12 @@ static int launch_hmc(const mc_program* p, const mc_run_config* cfg, void* state
     A.dpad = dpad_of(p->D);
     A.lds_floats = (int32_t)hmc_lds_floats(p, LDS);
     A.scratch_floats = scratch_of(p);
+    MetricDev M = {};
+    if constexpr (MET) {
+        const bool ml = LDS && cpb_of(WPC) * (A.lds_floats + 2 * (int64_t)A.dpad) * 4 <= kLdsArenaBudget;
+        if (ml) A.lds_floats += 2 * A.dpad;
+        M = metricdev_of(p, cfg->num_chains, metric, adapt, ml);
+    }
     const size_t lds = (size_t)cpb_of(WPC) * A.lds_floats * 4;
     const int64_t grid = (cfg->num_chains + cpb_of(WPC) - 1) / cpb_of(WPC);
     if constexpr (EX) {  // the program's expression terms compiled (jit.hip)
@@ -177,17 +187,26 @@ static int launch_hmc(const mc_program* p, const mc_run_config* cfg, void* state
         mc_chain_scalars* scal = (mc_chain_scalars*)b;
         float *sq = (float*)(b + qo), *sg = (float*)(b + go);
         TraceDev td = trace_of(tr);
-        void* args[] = {&ctx, &A, &scal, &sq, &sg, &samples, &td, &ws};
+        void* args[] = {&ctx, &A, &scal, &sq, &sg, &samples, &td, &ws, &M};  // (M: MET only)
         bool used = false;
         const int rc = jit_launch(p, "mc::k_hmc<" + std::to_string(WPC) + ", " +
-                                         (LDS ? "true" : "false") + ", true>",
+                                         (LDS ? "true" : "false") +
+                                         (MET ? ", true, true, mc::MetricDev>" : ", true>"),
                                   (unsigned)grid, block_of(WPC), lds, st, args, &used);
         if (rc != MC_OK || used) return rc;
     }
-    MC_HIP_TRY(allow_lds(k_hmc<WPC, LDS, EX>, lds));
-    hipLaunchKernelGGL((k_hmc<WPC, LDS, EX>), dim3((unsigned)grid), dim3(block_of(WPC)), lds, st,
-                       ctx_of(p), A, (mc_chain_scalars*)b, (float*)(b + qo), (float*)(b + go),
-                       samples, trace_of(tr), ws);
+    if constexpr (MET) {
+        auto kern = k_hmc<WPC, LDS, EX, true, MetricDev>;
+        MC_HIP_TRY(allow_lds(kern, lds));
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block_of(WPC)), lds, st, ctx_of(p), A,
+                           (mc_chain_scalars*)b, (float*)(b + qo), (float*)(b + go), samples,
+                           trace_of(tr), ws, M);
+    } else {
+        MC_HIP_TRY(allow_lds(k_hmc<WPC, LDS, EX>, lds));
+        hipLaunchKernelGGL((k_hmc<WPC, LDS, EX>), dim3((unsigned)grid), dim3(block_of(WPC)), lds,
+                           st, ctx_of(p), A, (mc_chain_scalars*)b, (float*)(b + qo),
+                           (float*)(b + go), samples, trace_of(tr), ws);
+    }
     MC_HIP_TRY(hipGetLastError());
     return MC_OK;
 }
@@ -234,6 +253,33 @@ extern "C" int mc_hmc_run(const mc_program* p, const mc_run_config* cfg, void* s
     return dispatch_tape(p, lds, [&](auto W, auto L, auto E) {
         return launch_hmc<decltype(W)::value, decltype(L)::value, decltype(E)::value>(
             p, cfg, state, samples, tr, w, st);
+    });
+}
+
+extern "C" int mc_hmc_run_metric(const mc_program* p, const mc_run_config* cfg, void* state,
+                                 float* samples, const mc_trace* tr, void* ws, int64_t ws_bytes,
+                                 void* metric, int32_t adapt, void* stream) {
+    int rc = check_cfg(p, cfg, state);
+    if (rc) return rc;
+    if (!metric) return fail(MC_ERR_INVALID, "metric buffer is NULL");
+    if (cfg->num_leapfrog_steps < 0) return fail(MC_ERR_INVALID, "num_leapfrog_steps < 0");
+    const bool sl_tape = sliced(p) && !use_lanes(p, cfg) && !interp_ok(p);
+    if ((sliced(p) && !sl_tape) || (lanes1(p) && use_lanes(p, cfg)))
+        return fail(MC_ERR_UNSUPPORTED,
+                    "a metric runs on the chain-per-workgroup kernel k_hmc only and this program "
+                    "is planned onto a sliced or lane-resident kernel: "
+                    "mc_program_set_slices(prog, 1) keeps it on k_hmc");
+    if (cfg->num_chains == 0 || cfg->iter_count == 0) return MC_OK;
+    ws_forget(ws);
+    const bool lds = hmc_use_lds(p);
+    const int64_t need = mc_hmc_workspace_bytes(p, cfg->num_chains);
+    if (!lds && (ws == nullptr || ws_bytes < need))
+        return fail(MC_ERR_INVALID, "workspace too small: need %lld bytes", (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    float* w = (float*)ws;
+    return dispatch_tape(p, lds, [&](auto W, auto L, auto E) {
+        return launch_hmc<decltype(W)::value, decltype(L)::value, decltype(E)::value, true>(
+            p, cfg, state, samples, tr, w, st, metric, adapt);
     });
 }
 

@@ -27,9 +27,13 @@ extern "C" int64_t mc_nuts_workspace_bytes(const mc_program* p, int64_t C, int32
     return tape;
 }
 
-template <int WPC, bool LDS, bool EX>
+// MET: the metric instantiation (metric.h) on the buffer `metric`; minv and
+// msqrt follow the arena in LDS when the two extra vectors still fit its budget
+// (the arena decision itself, and so the workspace, is the one without a metric)
+template <int WPC, bool LDS, bool EX, bool MET = false>
 static int launch_nuts(const mc_program* p, const mc_run_config* cfg, void* state,
-                       float* samples, const mc_trace* tr, float* ws, hipStream_t st) {
+                       float* samples, const mc_trace* tr, float* ws, hipStream_t st,
+                       void* metric = nullptr, int adapt = 0) {
     int64_t qo, go;
     mc_state_offsets(p, cfg->num_chains, &qo, &go);
     char* b = (char*)state;
@@ -39,6 +43,12 @@ static int launch_nuts(const mc_program* p, const mc_run_config* cfg, void* stat
     A.dpad = dpad_of(p->D);
     A.scratch_floats = scratch_of(p);
     A.lds_floats = (int32_t)nuts_lds_floats(p, cfg->max_tree_depth, LDS);
+    MetricDev M = {};
+    if constexpr (MET) {
+        const bool ml = LDS && cpb_of(WPC) * (A.lds_floats + 2 * (int64_t)A.dpad) * 4 <= kNutsLdsBudget;
+        if (ml) A.lds_floats += 2 * A.dpad;
+        M = metricdev_of(p, cfg->num_chains, metric, adapt, ml);
+    }
     size_t lds = (size_t)cpb_of(WPC) * A.lds_floats * 4;
     // the data pool after the chain groups when it fits as well
     const size_t dbytes = (p->h_data.size() + 3) / 4 * 16;
@@ -56,17 +66,26 @@ static int launch_nuts(const mc_program* p, const mc_run_config* cfg, void* stat
         mc_chain_scalars* scal = (mc_chain_scalars*)b;
         float *sq = (float*)(b + qo), *sg = (float*)(b + go);
         TraceDev td = trace_of(tr);
-        void* args[] = {&ctx, &A, &scal, &sq, &sg, &samples, &td, &ws};
+        void* args[] = {&ctx, &A, &scal, &sq, &sg, &samples, &td, &ws, &M};  // (M: MET only)
         bool used = false;
         const int rc = jit_launch(p, "mc::k_nuts<" + std::to_string(WPC) + ", " +
-                                         (LDS ? "true" : "false") + ", true>",
+                                         (LDS ? "true" : "false") +
+                                         (MET ? ", true, true, mc::MetricDev>" : ", true>"),
                                   (unsigned)grid, block_of(WPC), lds, st, args, &used);
         if (rc != MC_OK || used) return rc;
     }
-    MC_HIP_TRY(allow_lds(k_nuts<WPC, LDS, EX>, lds));
-    hipLaunchKernelGGL((k_nuts<WPC, LDS, EX>), dim3((unsigned)grid), dim3(block_of(WPC)), lds, st,
-                       ctx_of(p), A, (mc_chain_scalars*)b, (float*)(b + qo), (float*)(b + go),
-                       samples, trace_of(tr), ws);
+    if constexpr (MET) {
+        auto kern = k_nuts<WPC, LDS, EX, true, MetricDev>;
+        MC_HIP_TRY(allow_lds(kern, lds));
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block_of(WPC)), lds, st, ctx_of(p), A,
+                           (mc_chain_scalars*)b, (float*)(b + qo), (float*)(b + go), samples,
+                           trace_of(tr), ws, M);
+    } else {
+        MC_HIP_TRY(allow_lds(k_nuts<WPC, LDS, EX>, lds));
+        hipLaunchKernelGGL((k_nuts<WPC, LDS, EX>), dim3((unsigned)grid), dim3(block_of(WPC)), lds,
+                           st, ctx_of(p), A, (mc_chain_scalars*)b, (float*)(b + qo),
+                           (float*)(b + go), samples, trace_of(tr), ws);
+    }
     MC_HIP_TRY(hipGetLastError());
     return MC_OK;
 }
@@ -215,6 +234,33 @@ extern "C" int mc_nuts_run(const mc_program* p, const mc_run_config* cfg, void* 
     return dispatch_tape(p, lds, [&](auto W, auto L, auto E) {
         return launch_nuts<decltype(W)::value, decltype(L)::value, decltype(E)::value>(
             p, cfg, state, samples, tr, w, st);
+    });
+}
+
+extern "C" int mc_nuts_run_metric(const mc_program* p, const mc_run_config* cfg, void* state,
+                                  float* samples, const mc_trace* tr, void* ws, int64_t ws_bytes,
+                                  void* metric, int32_t adapt, void* stream) {
+    int rc = check_cfg(p, cfg, state);
+    if (rc) return rc;
+    if (!metric) return fail(MC_ERR_INVALID, "metric buffer is NULL");
+    if (cfg->max_tree_depth < 0 || cfg->max_tree_depth > kMaxTreeDepth)
+        return fail(MC_ERR_UNSUPPORTED, "max_tree_depth must be in [0, %d]", kMaxTreeDepth);
+    if (use_nuts_sliced(p, cfg->max_tree_depth) || use_nuts_lanes(p, cfg->max_tree_depth))
+        return fail(MC_ERR_UNSUPPORTED,
+                    "a metric runs on the chain-per-workgroup kernel k_nuts only and this program "
+                    "is planned onto a sliced or lane-resident kernel: "
+                    "mc_program_set_slices(prog, 1) keeps it on k_nuts");
+    if (cfg->num_chains == 0 || cfg->iter_count == 0) return MC_OK;
+    const int64_t need = mc_nuts_workspace_bytes(p, cfg->num_chains, cfg->max_tree_depth);
+    if (need > 0 && (ws == nullptr || ws_bytes < need))
+        return fail(MC_ERR_INVALID, "workspace too small: need %lld bytes", (long long)need);
+    if (ws) ws_forget(ws);
+    float* w = (float*)ws;
+    hipStream_t st = (hipStream_t)stream;
+    const bool lds = nuts_use_lds(p, cfg->max_tree_depth);
+    return dispatch_tape(p, lds, [&](auto W, auto L, auto E) {
+        return launch_nuts<decltype(W)::value, decltype(L)::value, decltype(E)::value, true>(
+            p, cfg, state, samples, tr, w, st, metric, adapt);
     });
 }
 

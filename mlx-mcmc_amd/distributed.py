@@ -25,6 +25,27 @@ def shard(total_chains: int, world: int, rank: int) -> Tuple[int, int]:
     return offset, count
 
 
+def shard_metric(inverse_mass_matrix, adapt_mass_matrix: bool, total_chains: int, world: int,
+                 rank: int) -> dict:
+    """The ``inverse_mass_matrix`` / ``adapt_mass_matrix`` keywords of rank's
+    ``hmc()`` / ``nuts()`` call: a per-chain [total_chains, D] metric is cut to
+    the rank's block of chains (``shard``); a dict or one [D] vector goes to
+    every rank as it is.  The metric is per chain and never pooled, so a
+    chain's draws do not depend on the sharding."""
+    import numpy as np
+
+    m = inverse_mass_matrix
+    if m is not None and not isinstance(m, dict):
+        a = np.asarray(m, np.float32)
+        if a.ndim == 2:
+            if a.shape[0] != total_chains:
+                raise ValueError(f"inverse_mass_matrix has {a.shape[0]} rows for "
+                                 f"{total_chains} chains")
+            offset, count = shard(total_chains, world, rank)
+            m = a[offset:offset + count]
+    return {"inverse_mass_matrix": m, "adapt_mass_matrix": bool(adapt_mass_matrix)}
+
+
 def gather_to_root(t, group=None) -> Optional[object]:
     """Gather every rank's [count_r, ...] tensor on rank 0, concatenated in rank
     (= global chain) order; other ranks get None.  Ranks may hold different

@@ -8,6 +8,7 @@ return types.
 """
 from __future__ import annotations
 
+import functools
 import time
 import warnings
 from dataclasses import dataclass, field
@@ -54,6 +55,35 @@ def _chunks(begin: int, end: int, every: int):
         it = nxt
 
 
+def _metric_array(inverse_mass_matrix, initial_params, num_chains: int):
+    """``inverse_mass_matrix`` as a float32 [D] or [C, D] array: a dict shaped
+    like ``initial_params`` (one [D] vector), or a flat array of either shape.
+    Raises ValueError on a wrong shape or an entry that is not finite and
+    positive (host-side: before any device work)."""
+    shapes = {k: np.asarray(_trace._to_numpy(v)).shape for k, v in initial_params.items()}
+    D = int(sum(int(np.prod(s)) if s else 1 for s in shapes.values()))
+    if isinstance(inverse_mass_matrix, dict):
+        if set(inverse_mass_matrix) != set(shapes):
+            raise ValueError("inverse_mass_matrix must have the keys of initial_params "
+                             f"{sorted(shapes)}, not {sorted(inverse_mass_matrix)}")
+        parts = []
+        for k, shp in shapes.items():
+            v = np.asarray(_trace._to_numpy(inverse_mass_matrix[k]), np.float32)
+            if v.shape != shp:
+                raise ValueError(f"inverse_mass_matrix['{k}'] has shape {v.shape}, "
+                                 f"expected {shp}")
+            parts.append(v.ravel())
+        a = np.concatenate(parts) if parts else np.empty(0, np.float32)
+    else:
+        a = np.asarray(_trace._to_numpy(inverse_mass_matrix), np.float32)
+        if a.shape not in ((D,), (num_chains, D)):
+            raise ValueError(f"inverse_mass_matrix has shape {a.shape}, expected ({D},) or "
+                             f"({num_chains}, {D})")
+    if not np.all(np.isfinite(a) & (a > 0)):
+        raise ValueError("inverse_mass_matrix entries must be finite and positive")
+    return np.ascontiguousarray(a, np.float32)
+
+
 def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int,
                 num_warmup: int, step_size: float, target_accept: float,
                 adapt_step_size: bool, key, num_leapfrog_steps: int = 10,
@@ -61,7 +91,8 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
                 slice_mode: str = "reference", progress: bool = True,
                 progress_every: Optional[int] = None, return_trace: bool = False,
                 keep_on_device: bool = False, initial_positions=None, num_slices: int = 0,
-                slice_kernel: str = "auto"):
+                slice_kernel: str = "auto", inverse_mass_matrix=None,
+                adapt_mass_matrix: bool = False):
     import torch
 
     if algorithm not in ("hmc", "nuts"):
@@ -69,9 +100,22 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
     if num_samples < 0 or num_warmup < 0:
         raise ValueError("num_samples and num_warmup must be non-negative")
     k = _as_key(key)
+    C = int(num_chains)
+    if C < 1:
+        raise ValueError("num_chains must be >= 1")
+    # a diagonal metric (csrc/metric.h) runs on the chain-per-workgroup tape
+    # kernels only: the program is planned as num_slices=1 / nuts_kernel="tape"
+    use_metric = inverse_mass_matrix is not None or bool(adapt_mass_matrix)
+    minv0 = (_metric_array(inverse_mass_matrix, initial_params, C)
+             if inverse_mass_matrix is not None else None)
+    if use_metric:
+        if num_slices > 1 or slice_kernel != "auto":
+            raise ValueError("a mass matrix runs on the chain-per-workgroup kernels: leave "
+                             "num_slices at 0 or 1 and slice_kernel at 'auto'")
+        num_slices = 1
     program = _trace.compile_model(log_prob_fn, initial_params, slices=num_slices,
                                    slice_kernel=slice_kernel)
-    if algorithm == "nuts" and num_slices == 0 and slice_kernel == "auto":
+    if algorithm == "nuts" and num_slices == 0 and slice_kernel == "auto" and not use_metric:
         # a large regression's affine terms as expression terms: the sliced
         # NUTS kernel instead of the tape (_trace.nuts_program)
         program = _trace.nuts_program(program, max_tree_depth)
@@ -87,14 +131,13 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
         # on a 2-4x slower kernel; say so instead of degrading silently
         warnings.warn(f"{note}; running on the {program.slice_kernel} kernel", RuntimeWarning,
                       stacklevel=3)
-    C = int(num_chains)
-    if C < 1:
-        raise ValueError("num_chains must be >= 1")
     if initial_positions is None:
         q0 = layout.flatten(initial_params)
     else:
         q0 = np.asarray(initial_positions, np.float32).reshape(C, layout.size)
     chains = _engine.ChainSet(program, C, q0, step_size)
+    if use_metric:
+        chains.set_metric(minv0)
     total = num_warmup + num_samples
     samples = torch.empty((C, max(num_samples, 1), layout.size), dtype=torch.float32,
                           device=chains.device)
@@ -105,11 +148,15 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
     if algorithm == "hmc":
         cfg["num_leapfrog_steps"] = num_leapfrog_steps
         launch = chains.run_hmc
+        if use_metric:
+            launch = functools.partial(chains.run_hmc_metric, adapt=bool(adapt_mass_matrix))
         every = progress_every or 500
     else:
         cfg["max_tree_depth"] = max_tree_depth
         cfg["slice_mode"] = {"reference": 0, "exact": 1}[slice_mode]
         launch = chains.run_nuts
+        if use_metric:
+            launch = functools.partial(chains.run_nuts_metric, adapt=bool(adapt_mass_matrix))
         every = progress_every or 250
     out = (lambda *a: print(*a)) if progress else (lambda *a: None)
 
@@ -197,6 +244,11 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
                             else program.slice_kernel)
     if note and algorithm == "hmc":
         info.extra["kernel_note"] = note
+    if use_metric:
+        info.extra["kernel_note"] = ("a mass matrix runs on the chain-per-workgroup tape kernel "
+                                     f"(k_{algorithm}), as num_slices=1 does")
+        info.extra["inverse_mass_matrix"] = chains.inverse_mass().cpu().numpy()
+        info.extra["metric_updates"] = chains.metric_scalars()["n_updates"].copy()
     host = flat.cpu().numpy()
     per_name = layout.unflatten(host)  # name -> [C, S, *shape]
     if C == 1:

@@ -20,6 +20,12 @@ chain per workgroup, >= 2 data slices per chain: csrc/sliced.h), and
 csrc/lanes.h when the layout qualifies, "interpreter": csrc/sliced.h,
 "lanes"; with ``num_slices=1`` "lanes" runs the unsliced program on the
 lane-resident kernel with one slice).
+``inverse_mass_matrix`` (a dict shaped like ``initial_params``, or a flat [D]
+or [num_chains, D] array) sets a per-chain diagonal metric M = diag(1 / minv)
+and ``adapt_mass_matrix=True`` adapts it per chain during warmup (Stan's
+windows, csrc/metric.h); either one runs the chain-per-workgroup kernel
+``k_hmc``.  ``RunInfo.extra["inverse_mass_matrix"]`` holds the final [C, D]
+metric, which a second run can start from.
 Vector-valued parameters are supported (the reference's ``float()`` store,
 hmc.py:192, rejects them — SURVEY Q6).
 """
@@ -31,7 +37,8 @@ from ._driver import run_sampler
 def hmc(log_prob_fn, initial_params, num_samples=1000, num_warmup=1000, step_size=0.1,
         num_leapfrog_steps=10, adapt_step_size=True, target_accept=0.8, key=None, *,
         num_chains=1, chain_offset=0, progress=True, return_info=False, return_trace=False,
-        keep_on_device=False, initial_positions=None, num_slices=0, slice_kernel="auto"):
+        keep_on_device=False, initial_positions=None, num_slices=0, slice_kernel="auto",
+        inverse_mass_matrix=None, adapt_mass_matrix=False):
     """Hamiltonian Monte Carlo sampler using gradient information.
 
     Returns ``(samples, acceptance_rate)`` like the reference: ``samples`` maps
@@ -46,7 +53,8 @@ def hmc(log_prob_fn, initial_params, num_samples=1000, num_warmup=1000, step_siz
         key=key, num_leapfrog_steps=num_leapfrog_steps, num_chains=num_chains,
         chain_offset=chain_offset, progress=progress, return_trace=return_trace,
         keep_on_device=keep_on_device, initial_positions=initial_positions,
-        num_slices=num_slices, slice_kernel=slice_kernel)
+        num_slices=num_slices, slice_kernel=slice_kernel,
+        inverse_mass_matrix=inverse_mass_matrix, adapt_mass_matrix=adapt_mass_matrix)
     if return_info:
         return samples, rate, info
     return samples, rate

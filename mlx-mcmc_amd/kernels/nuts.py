@@ -21,7 +21,14 @@ slice variable: u = f32 exp(log u) rounds to the smallest denormal (log u =
 ~-103.28, SURVEY Q7's ~-103.3) down to ln 2^-150 ~ -103.97 and to 0 below it,
 which switches the slice test off (log u = -inf)
 (nuts.py:236-237); ``"exact"`` keeps log u in double precision.
-Keyword-only additions as for ``hmc()``.
+Keyword-only additions as for ``hmc()``, ``inverse_mass_matrix`` and
+``adapt_mass_matrix`` among them: a per-chain diagonal metric, adapted during
+warmup in Stan's windows with dual averaging restarted at each update
+(csrc/metric.h); such a run takes ``k_nuts`` as ``nuts_kernel="tape"`` does.
+(On a model with constrained parameters the restart's first, ~15x longer step
+can meet the reference's NaN -> alpha = 1 rule and run the step size away —
+DESIGN section 4; adapt with ``adapt_step_size=False``, or pass a metric adapted
+earlier as ``inverse_mass_matrix``.)
 """
 from __future__ import annotations
 
@@ -34,7 +41,8 @@ def nuts(log_prob_fn, initial_params, num_samples=1000, num_warmup=1000, step_si
          max_tree_depth=10, adapt_step_size=True, target_accept=0.65, key=None, *,
          num_chains=1, chain_offset=0, slice_mode="reference", progress=True,
          return_info=False, return_trace=False, keep_on_device=False,
-         initial_positions=None, nuts_kernel="auto", num_slices=0):
+         initial_positions=None, nuts_kernel="auto", num_slices=0,
+         inverse_mass_matrix=None, adapt_mass_matrix=False):
     """No-U-Turn Sampler (NUTS) for efficient HMC sampling.
 
     Returns ``(samples, acceptance_rate)`` like the reference, where the rate
@@ -50,7 +58,8 @@ def nuts(log_prob_fn, initial_params, num_samples=1000, num_warmup=1000, step_si
         chain_offset=chain_offset, slice_mode=slice_mode, progress=progress,
         return_trace=return_trace, keep_on_device=keep_on_device,
         initial_positions=initial_positions,
-        num_slices=1 if nuts_kernel == "tape" else int(num_slices))
+        num_slices=1 if nuts_kernel == "tape" else int(num_slices),
+        inverse_mass_matrix=inverse_mass_matrix, adapt_mass_matrix=adapt_mass_matrix)
     if return_info:
         return samples, rate, info
     return samples, rate
