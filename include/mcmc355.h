@@ -481,6 +481,16 @@ int mc_debug_expr_jit_compile(const mc_program* prog, const char* kernel);
  * mc_debug_expr_jit_source / _compile take a "mc::k_hmc_lr<...>" kernel name
  * and give / compile the lane-resident source (jit.hip gen_lane_source).  */
 int mc_debug_lane_plan_host(mc_program* prog, int32_t num_slices);
+/* host-only program (mc_debug_program_host_only): plan it with S slices and
+ * write one 64-bit FNV-1a digest per host table: 13 of the slice plan (its
+ * scalars S, Lp, Pmax, Dsh, nitems, sdata_floats, combine, then terms, sterms,
+ * data, index, blocks, gidx), then 24 of the lane plan (ok, rs, rep, S, Dsh,
+ * nitems, sdata_floats, shl, shxf, shid, n_generic, fast, form, has_xf,
+ * has_expr, nuts_expr, bundle, then terms, data, blocks, gidx, sterms, rng,
+ * gx_off); n_out >= 37.  Returns the planner's status: all digests 0 when the
+ * slice planner refuses; the lane digests 0 and MC_ERR_UNSUPPORTED (the reason
+ * in mc_last_error) when only the lane planner declines.                    */
+int mc_debug_plan_digest(mc_program* prog, int32_t num_slices, uint64_t* out, int32_t n_out);
 int64_t mc_debug_expr_jit_lane_source(const mc_program* prog, char* buf, int64_t cap);
 /* Test hooks (host code, no device): the samplers' Box-Muller pair from two
  * Philox words per pair (words [n][2] -> out [n][2] f32) and their f32 log

@@ -419,7 +419,7 @@ class Affine:
         gather), so the result is the same affine form, rounded per element as
         the reference's indexed MLX array.  A gather that repeats parameters
         anywhere but in the loc over a data x (the fused affine terms' rule,
-        api.hip) makes it an expression instead."""
+        program.hip) makes it an expression instead."""
         loc, x = _index_operand(self.loc, item), _index_operand(self.x, item)
         x_data = x is None or not isinstance(x, Param)
         if _repeats(x) or (_repeats(loc) and not x_data):
@@ -1390,7 +1390,7 @@ def _has_data_leaf(e: "Expr") -> bool:
 
 def _own_prior_like(t: Term) -> bool:
     """A scalar term the sliced kernels evaluate as a shared parameter's own
-    prior (api.hip plan_lanes LrSterm::own): Normal / HalfNormal of an
+    prior (plan_lanes.hip lane_sterms LrSterm::own): Normal / HalfNormal of an
     untransformed scalar parameter with constant loc and scale."""
     return (t.dist in (_lib.MC_DIST_NORMAL, _lib.MC_DIST_HALFNORMAL) and t.aff is None
             and t.value.kind == _lib.MC_OP_PSCALAR and t.value.transform == 0

@@ -17,7 +17,7 @@
 //   segmented  terms gathered through a sorted group index (hierarchical
 //              likelihoods): each lane owns one run of one group in a
 //              host-built tiled layout, keeps theta_group in a register and
-//              sums the group's cotangent in a register (csrc/api.hip
+//              sums the group's cotangent in a register (csrc/program.hip
 //              build_segments).
 // Terms with a broadcast (uniform) scale accumulate moments per lane —
 // count, sum d, sum d^2 with d = value - loc — and form log p and every

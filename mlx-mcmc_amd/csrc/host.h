@@ -1,7 +1,8 @@
 // host.h — internal host-side declarations shared by the translation units of
-// libmcmc355.so (api.hip: program builder, planners, tape / diagnostics
-// launches and the rest of the C-ABI; run_hmc.hip, run_mh.hip, run_nuts.hip:
-// the sampler launches).  Helpers are `inline` so that every unit shares one
+// libmcmc355.so (program.hip: program builder, slicing policy and queries;
+// plan_slices.hip, plan_lanes.hip: the planners, declared in plan.h; api.hip:
+// tape / state / metric / diagnostics launches and the rest of the C-ABI;
+// run_hmc.hip, run_mh.hip, run_nuts.hip: the sampler launches).  Helpers are `inline` so that every unit shares one
 // definition (and one copy of the caches and workspace tag tables).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -57,6 +58,20 @@ inline int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess)                                                           \
             return fail(MC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));      \
     } while (0)
+
+// f32 constants exactly as the reference forms them (normal.py:31,
+// halfnormal.py:31-32): log_norm = -0.5 * f32 log(f32(2*pi)), log2 = f32 log 2.
+inline float c_log_norm() {
+    const float two_pi = (float)(2.0 * 3.141592653589793);
+    const float l = (float)std::log((double)two_pi);
+    return -0.5f * l;
+}
+inline float c_log2() { return (float)std::log(2.0); }
+inline float dist_c0(int dist) {
+    if (dist == MC_DIST_NORMAL) return c_log_norm();
+    if (dist == MC_DIST_HALFNORMAL) return c_log2() + c_log_norm();
+    return 0.0f;
+}
 
 // ---------------------------------------------------------------------------
 // program
@@ -251,7 +266,7 @@ inline bool affine_lanes_ok(const mc_program* p) {
 // or, beside those, parameter-vector and gather leaves that all read through
 // one element -> group map (a PVEC leaf: the identity): a grouped term, its
 // elements tiled by the (lane, slot) that owns the group's bundle of private
-// parameters (alpha_g, beta_g; api.hip plan_lanes).  expr_term_class: 0 a
+// parameters (alpha_g, beta_g; plan_lanes.hip).  expr_term_class: 0 a
 // chunk term, 1 a grouped term (its distinct vectors' offsets into *vecs, its
 // map into *gmap), -1 neither (why).  Every term of the program must qualify
 // (else the program stays on the tape kernels).

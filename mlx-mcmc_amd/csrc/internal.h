@@ -1,5 +1,5 @@
 // internal.h — device-side program representation shared by the host code
-// that builds it (api.hip) and the kernels that execute it (eval.h, hmc.h,
+// that builds it (program.hip) and the kernels that execute it (eval.h, hmc.h,
 // nuts.h).  Not part of the C-ABI.
 #pragma once
 #include <stdint.h>

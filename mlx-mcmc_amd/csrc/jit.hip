@@ -102,7 +102,7 @@ void gen_term(std::ostringstream& o, const DevTerm& T, const DevExprNode* N) {
             o << "  const float c" << k << " = N[" << k << "].leaf.cval;\n";
         }
     }
-    // the pass count is a function of the leaves' passes (api.hip
+    // the pass count is a function of the leaves' passes (program.hip
     // build_expr_term), so it is a constant here: one pass (the usual case)
     // leaves no pass tests in the element code
     int npass_c = 1;

@@ -24,7 +24,7 @@
 //     slice), so all replicas of a shared parameter stay bit-identical and
 //     every slice takes the same accept decision.  The scalar terms (priors of
 //     the shared parameters) are then added in term order.
-// Eligibility (host planner, api.hip plan_lanes): S <= 16, <= kLrMaxShared
+// Eligibility (host planner, plan_lanes.hip plan_lanes): S <= 16, <= kLrMaxShared
 // shared parameters, <= 64 * kLrMaxSlots private parameters per slice, and
 // every per-element parameter operand private.  Results equal k_hmc_sl's up
 // to fp32 summation order; runs are bit-reproducible and independent of how
@@ -1099,7 +1099,7 @@ k_hmc_lr(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
         }
 
     const int L = cfg.num_leapfrog_steps;
-    uint32_t epoch = ebase;  // tags continue across launches (api.hip ws_reserve)
+    uint32_t epoch = ebase;  // tags continue across launches (host.h ws_reserve)
     bool ok = true;
     // granules: one 128-byte line per (wave, slice) record, written by one
     // store instruction of one wave (lane = pair), so a polled line is never

@@ -3,7 +3,7 @@
 // (lanes.h; reference hmc.py:7-206 per chain) with everything a fast-form
 // program does not need compiled out.
 //
-// Fast form (host planner, api.hip plan_lanes: LanePlan::fast): every slice
+// Fast form (host planner, plan_lanes.hip plan_lanes: LanePlan::fast): every slice
 // holds at most one swept term — y ~ N(theta[g], scale), value data, loc the
 // lane's private parameter, scale shared or constant: moment sums over the
 // private parameter's elements — and at most one direct term — theta ~
@@ -557,7 +557,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
         g[r] = (f2){R0.g[r][0], R0.g[r][1]};
         p[r] = (f2){0.f, 0.f};
     }
-    // the lane RNG plan (api.hip plan_lane_rng), when the planner made one
+    // the lane RNG plan (plan_lanes.hip plan_lane_rng), when the planner made one
     const bool rngp = P.rng != nullptr;
     int4 rw = {0, 0, 0, 0};
     if (rngp) rw = P.rng[(int64_t)slice * 64 + j];
@@ -680,7 +680,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
     };
 
     const int L = cfg.num_leapfrog_steps;
-    uint32_t epoch = ebase;  // tags continue across launches (api.hip ws_reserve)
+    uint32_t epoch = ebase;  // tags continue across launches (host.h ws_reserve)
     bool ok = true;
     // one 128-byte line per (wave, slice) record; lanes publish the pairs
     // they hold after the reduce-scatter, pass ps of the poll reads pair
@@ -756,7 +756,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
         f2 k0p = {0.f, 0.f};
         float logu_acc[2] = {0.f, 0.f};  // the chains' accept logs (lane RNG plan)
         if (rngp) {
-            // the lane RNG plan (api.hip plan_lane_rng): this lane's Philox
+            // the lane RNG plan (plan_lanes.hip plan_lane_rng): this lane's Philox
             // block — a momentum block of one chain or a chain's accept draw —
             // and both Box-Muller pairs of it; the accept lanes' first log is
             // the accept log (mc_logf_unit of the same uniform transform the

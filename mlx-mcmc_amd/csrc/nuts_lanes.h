@@ -44,7 +44,7 @@ __host__ __device__ constexpr int64_t nuts_lr_draw_words(int max_depth) {
 // every scalar term is an own prior (the planner checks it): the generic
 // per-element and scalar-term paths are compiled out, and with them their
 // register demand (inlined, it spills the tree walk's state).
-// SPEC 2 (register-only programs, api.hip lanes_register_only): no broadcast
+// SPEC 2 (register-only programs, run_nuts.hip lanes_register_only): no broadcast
 // parameter, no scalar term and one slice term with at most one element per
 // (lane, slot) — a data-scale term (config 5's theta_i ~ N(0, s_i)) or a
 // direct term with constant loc and scale (theta_i ~ N(m, s)): the gradient
@@ -278,7 +278,7 @@ k_nuts_lr(LrCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, 
         }
     };
     auto derive = [&]() {
-        sh.v = sh.q;  // (NUTS programs carry no transformed parameter: api.hip use_nuts_lanes)
+        sh.v = sh.q;  // (NUTS programs carry no transformed parameter: run_nuts.hip use_nuts_lanes)
         sh.is = 1.0f / sh.q;
         sh.iv = 1.0f / (sh.q * sh.q);
         sh.lg = logf(sh.q);

@@ -318,7 +318,7 @@ k_nuts_sl(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
     const uint32_t chain_id = (uint32_t)(cfg.chain_offset + c);
     const int64_t it_end = cfg.iter_begin + cfg.iter_count;
     int64_t n_grad = 0;
-    uint32_t epoch = ebase;  // tags continue across launches (api.hip ws_reserve)
+    uint32_t epoch = ebase;  // tags continue across launches (host.h ws_reserve)
     bool ok = true;
     MC_STAMP_INIT
     // XL: the block's slices share an XCD (sliced.h xcd_announce / xcd_agree;

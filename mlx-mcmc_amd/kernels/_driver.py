@@ -41,7 +41,7 @@ class RunInfo:
     extra: Dict = field(default_factory=dict)
 
 
-# csrc/api.hip kLrAutoMinElements: the automatic plan slices programs of at
+# csrc/host.h kLrAutoMinElements: the automatic plan slices programs of at
 # least this many elements (and the lane-resident kernel is what pays for it)
 _LANES_WARN_ELEMENTS = 2048
 

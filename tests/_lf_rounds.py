@@ -23,4 +23,4 @@ ROUNDS = {
     "round6": ([0] + _cyc(11, lambda i: 96 + i % 8), 24, 6, 103, 1087),
 }
 NAMES = sorted(ROUNDS)
-PLANNED_REP = 4     # api.hip plan_lanes: min(16, 64 / 16) lanes per parameter for 12 groups
+PLANNED_REP = 4     # plan_lanes.hip plan_lanes: min(16, 64 / 16) lanes per parameter for 12 groups

@@ -8,7 +8,7 @@ remainder fixed by the shape and a masked tail of 0 or 1 element.  PATTERNS
 names run lengths that reach the other regimes of every sweep routine
 (lanes_fast.h lf_moments, lanes.h lr_moments, nuts_sliced.h nsl_moments,
 mh_sliced.h msl_sumsq, sliced.h run_moments2, the tape's segment tiles) and
-of the lane planner (api.hip plan_lanes: rs slots, rep lane groups).
+of the lane planner (plan_lanes.hip plan_lanes: rs slots, rep lane groups).
 
 The model (mu, tau, sigma scalars; theta[G]):
     mu ~ N(0, 10), tau ~ HalfNormal(5), sigma ~ HalfNormal(5),

@@ -1,5 +1,5 @@
 """Gathered-parameter expression terms on the lane-resident layout, on the
-CPU (csrc/host.h expr_term_class, api.hip plan_slices / plan_lanes bundles,
+CPU (csrc/host.h expr_term_class, plan_slices.hip plan_bundles, plan_lanes.hip deal,
 jit.hip gen_lane_term's grouped form; hiprtc cross-compiles gfx950 without a
 device): the planner takes `alpha[g] + beta[g] * x` likelihoods, deals whole
 bundles of private parameters to a lane's consecutive slots, and the

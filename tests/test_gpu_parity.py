@@ -316,7 +316,7 @@ def _measurement(ns, D=100):
 @pytest.mark.parametrize("model", ["iso", "illcond", "measurement"])
 def test_nuts_register_only_trees_match_oracle(gpu, model):
     """k_nuts_lr's register-only variant (one Normal term, one element per
-    parameter, constant or data scale; api.hip lanes_register_only): identical
+    parameter, constant or data scale; run_nuts.hip lanes_register_only): identical
     tree depths and leaf counts to the oracle for the first iterations, on a
     direct term with constant loc / scale (iso), a data-scale term with the
     value private (illcond, config 5) and with the loc private (measurement)."""

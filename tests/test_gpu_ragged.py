@@ -11,7 +11,7 @@ pipelined rounds or more, one remainder, a tail of 0 or 1.  Here runs are
 reloads it), 32..54 (remainders 0..3, tails of 0..7 across a float4
 boundary), 1..3 beside 301, spread over 2 and 4 register slots with the last
 slot part-filled, and split over lane groups of 2, 8 and 16 with members
-left empty (api.hip plan_lanes).
+left empty (plan_lanes.hip plan_lanes).
 
   * the tape (mc_logp_grad) at 4 perturbed points, sorted and shuffled group
     index;
