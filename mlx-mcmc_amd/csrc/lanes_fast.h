@@ -727,6 +727,53 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
         xpoll = xcd_announce(xslots, S, slice, ebase + 1, wave == 0 && j == 0);
     static_assert(NPAIR <= 15, "granule 15 of a record line is the XCD handshake's");
     const int64_t it_end = cfg.iter_begin + cfg.iter_count;
+    // The lane RNG plan's draws of iteration `itd` (plan_lanes.hip plan_lane_rng):
+    // this lane's Philox block — a momentum block of one chain or a chain's
+    // accept draw — and both Box-Muller pairs of it; the accept lanes' first
+    // log is the accept log (mc_logf_unit of the same uniform transform the
+    // per-lane path uses); the normals are fetched from their lanes.  They
+    // depend on the counters alone, so an iteration's are drawn while the
+    // last step of the iteration before waits for its exchange (nothing else
+    // covers that wait: no sweep follows the last step), the launch's first
+    // ahead of the loop — in the kernels of the Large shape's layout
+    // (DRAW_AHEAD: those with the sweep's prefetch, see PRE above); every
+    // other instantiation draws at the iteration's start, as before.
+    constexpr bool DRAW_AHEAD = RS == 1 && CF && (SPEC & LFS_REP1) != 0;
+    f2 nx_z[RS];
+    float nx_sh = 0.0f, nx_lu[2] = {0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < RS; ++r) nx_z[r] = (f2){0.f, 0.f};
+    auto draw_plan = [&](int64_t itd) {
+        const int kind = rw.x & 7;
+        const bool acl = kind >= 3;
+        const int csel = (kind == 2 || kind == 4) ? 1 : 0;
+        const mc_u32x4 rr =
+            mc_draw(cfg.seed, (uint32_t)(cfg.chain_offset + (csel ? cc[1] : cc[0])),
+                    (uint32_t)itd, acl ? MC_RNG_TAG_ACCEPT : MC_RNG_TAG_MOMENTUM, 0,
+                    acl ? 0u : ((uint32_t)rw.x >> 3));
+        const float la = mc_logf_unit(acl ? mc_u01_f32(rr.x) : mc_u01_boxf(rr.x));
+        const float lb = mc_logf_unit(mc_u01_boxf(rr.z));
+        float z[4];
+        mc_box_muller_log(la, rr.y, &z[0], &z[1]);
+        mc_box_muller_log(lb, rr.w, &z[2], &z[3]);
+        nx_lu[0] = rl(la, racc0);
+        nx_lu[1] = rl(la, racc1);
+        auto fetch = [&](int src, int comp) {
+            float v = __shfl(z[0], src);
+            const float v1 = __shfl(z[1], src), v2 = __shfl(z[2], src), v3 = __shfl(z[3], src);
+            v = comp == 1 ? v1 : v;
+            v = comp == 2 ? v2 : v;
+            return comp == 3 ? v3 : v;
+        };
+#pragma unroll
+        for (int r = 0; r < RS; ++r) {
+            const int word = (r < 2 ? rw.y : rw.z) >> (14 * (r & 1));
+            const int comp = (word >> 12) & 3;
+            nx_z[r] = (f2){fetch(word & 63, comp), fetch((word >> 6) & 63, comp)};
+        }
+        nx_sh = fetch(sh_src, xg & 3);
+    };
+    if (DRAW_AHEAD && rngp && cfg.iter_count > 0) draw_plan(cfg.iter_begin);
     for (int64_t it = cfg.iter_begin; it < it_end && ok; ++it) {
         MC_STAMP_DECL
         const bool warm = it < cfg.num_warmup;
@@ -756,43 +803,58 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
         f2 k0p = {0.f, 0.f};
         float logu_acc[2] = {0.f, 0.f};  // the chains' accept logs (lane RNG plan)
         if (rngp) {
-            // the lane RNG plan (plan_lanes.hip plan_lane_rng): this lane's Philox
-            // block — a momentum block of one chain or a chain's accept draw —
-            // and both Box-Muller pairs of it; the accept lanes' first log is
-            // the accept log (mc_logf_unit of the same uniform transform the
-            // per-lane path uses); the normals are fetched from their lanes
-            const int kind = rw.x & 7;
-            const bool acl = kind >= 3;
-            const int csel = (kind == 2 || kind == 4) ? 1 : 0;
-            const mc_u32x4 rr =
-                mc_draw(cfg.seed, (uint32_t)(cfg.chain_offset + (csel ? cc[1] : cc[0])),
-                        (uint32_t)it, acl ? MC_RNG_TAG_ACCEPT : MC_RNG_TAG_MOMENTUM, 0,
-                        acl ? 0u : ((uint32_t)rw.x >> 3));
-            const float la = mc_logf_unit(acl ? mc_u01_f32(rr.x) : mc_u01_boxf(rr.x));
-            const float lb = mc_logf_unit(mc_u01_boxf(rr.z));
-            float z[4];
-            mc_box_muller_log(la, rr.y, &z[0], &z[1]);
-            mc_box_muller_log(lb, rr.w, &z[2], &z[3]);
-            logu_acc[0] = rl(la, racc0);
-            logu_acc[1] = rl(la, racc1);
-            auto fetch = [&](int src, int comp) {
-                float v = __shfl(z[0], src);
-                const float v1 = __shfl(z[1], src), v2 = __shfl(z[2], src), v3 = __shfl(z[3], src);
-                v = comp == 1 ? v1 : v;
-                v = comp == 2 ? v2 : v;
-                return comp == 3 ? v3 : v;
-            };
+            if constexpr (DRAW_AHEAD) {
+                // this iteration's draws, made by draw_plan at the launch's
+                // start or in the shadow of the last exchange of the
+                // iteration before
+                logu_acc[0] = nx_lu[0];
+                logu_acc[1] = nx_lu[1];
 #pragma unroll
-            for (int r = 0; r < RS; ++r) {
-                const int word = (r < 2 ? rw.y : rw.z) >> (14 * (r & 1));
-                const int comp = (word >> 12) & 3;
-                const f2 zz = {fetch(word & 63, comp), fetch((word >> 6) & 63, comp)};
-                if (gk[r] < 0) continue;  // (an empty slot's p stays 0: its g is always 0)
-                p[r] = zz;
-                if (lead) k0p += zz * zz;
+                for (int r = 0; r < RS; ++r) {
+                    if (gk[r] < 0) continue;  // (an empty slot's p stays 0: its g is always 0)
+                    p[r] = nx_z[r];
+                    if (lead) k0p += nx_z[r] * nx_z[r];
+                }
+                sh.p = xon ? nx_sh : 0.0f;
+            } else {
+                // the lane RNG plan (plan_lanes.hip plan_lane_rng): this lane's Philox
+                // block — a momentum block of one chain or a chain's accept draw —
+                // and both Box-Muller pairs of it; the accept lanes' first log is
+                // the accept log (mc_logf_unit of the same uniform transform the
+                // per-lane path uses); the normals are fetched from their lanes
+                const int kind = rw.x & 7;
+                const bool acl = kind >= 3;
+                const int csel = (kind == 2 || kind == 4) ? 1 : 0;
+                const mc_u32x4 rr =
+                    mc_draw(cfg.seed, (uint32_t)(cfg.chain_offset + (csel ? cc[1] : cc[0])),
+                            (uint32_t)it, acl ? MC_RNG_TAG_ACCEPT : MC_RNG_TAG_MOMENTUM, 0,
+                            acl ? 0u : ((uint32_t)rw.x >> 3));
+                const float la = mc_logf_unit(acl ? mc_u01_f32(rr.x) : mc_u01_boxf(rr.x));
+                const float lb = mc_logf_unit(mc_u01_boxf(rr.z));
+                float z[4];
+                mc_box_muller_log(la, rr.y, &z[0], &z[1]);
+                mc_box_muller_log(lb, rr.w, &z[2], &z[3]);
+                logu_acc[0] = rl(la, racc0);
+                logu_acc[1] = rl(la, racc1);
+                auto fetch = [&](int src, int comp) {
+                    float v = __shfl(z[0], src);
+                    const float v1 = __shfl(z[1], src), v2 = __shfl(z[2], src), v3 = __shfl(z[3], src);
+                    v = comp == 1 ? v1 : v;
+                    v = comp == 2 ? v2 : v;
+                    return comp == 3 ? v3 : v;
+                };
+    #pragma unroll
+                for (int r = 0; r < RS; ++r) {
+                    const int word = (r < 2 ? rw.y : rw.z) >> (14 * (r & 1));
+                    const int comp = (word >> 12) & 3;
+                    const f2 zz = {fetch(word & 63, comp), fetch((word >> 6) & 63, comp)};
+                    if (gk[r] < 0) continue;  // (an empty slot's p stays 0: its g is always 0)
+                    p[r] = zz;
+                    if (lead) k0p += zz * zz;
+                }
+                const float zs = fetch(sh_src, xg & 3);
+                sh.p = xon ? zs : 0.0f;
             }
-            const float zs = fetch(sh_src, xg & 3);
-            sh.p = xon ? zs : 0.0f;
         } else {
 #pragma unroll
             for (int r = 0; r < RS; ++r) {
@@ -883,10 +945,11 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
         // K1 items, log p) nor its uniform branches and their live masks:
         // 0 first (l = 0 < L - 1), 1 intermediate, 2 last (l = L - 1 > 0),
         // 3 the only step (L = 1).  Returns false on an exchange timeout.
+        // ahead: called by a last step between its publish and its poll.
         // PAR: the record lines' parity when the caller knows it (an
         // intermediate step, compiled once per parity: the publish and poll
         // addresses are then fixed registers, no per-step selects), else -1
-        auto step = [&](int l, auto kind, auto parc) -> bool {
+        auto step = [&](int l, auto kind, auto parc, auto& ahead) -> bool {
             constexpr int KIND = decltype(kind)::value;
             constexpr int PAR = decltype(parc)::value;
             constexpr bool FIRST = KIND == 0 || KIND == 3, LAST = KIND == 2 || KIND == 3;
@@ -1132,6 +1195,8 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                 drift_private(true);
                 sweep(M1, M2, pre);
             }
+            // the last step: the next iteration's draws, while the records travel
+            if constexpr (LAST) ahead();
             MC_STAMP(8);
             if (!X1) poll_issue();
             auto poll_eval = [&]() {
@@ -1223,14 +1288,21 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             MC_STAMP(4);
             return true;
         };
+        // (handed to the step, not captured by it: a capture the other
+        // instantiations never use still changed their register allocation)
+        auto draw_next = [&]() {
+            if constexpr (DRAW_AHEAD) {
+                if (rngp && it + 1 < it_end) draw_plan(it + 1);
+            }
+        };
         const std::integral_constant<int, -1> rtpar;
         if (L == 1) {
-            ok = step(0, std::integral_constant<int, 3>(), rtpar);
+            ok = step(0, std::integral_constant<int, 3>(), rtpar, draw_next);
         } else {
-            ok = step(0, std::integral_constant<int, 0>(), rtpar);
+            ok = step(0, std::integral_constant<int, 0>(), rtpar, draw_next);
             const std::integral_constant<int, 1> mid;
             if (X1) {
-                for (int l = 1; ok && l < L - 1; ++l) ok = step(l, mid, rtpar);
+                for (int l = 1; ok && l < L - 1; ++l) ok = step(l, mid, rtpar, draw_next);
             } else {
                 // the intermediate steps, two per loop trip: line parity 0 then
                 // parity 1, straight-line, so every loop-carried value is in
@@ -1242,16 +1314,16 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                 const std::integral_constant<int, 1> par1;
                 int n = L - 2;
                 if (n > 0 && !(epoch & 1)) {  // (the next tag is odd: parity 1)
-                    ok = step(1, mid, par1);
+                    ok = step(1, mid, par1, draw_next);
                     --n;
                 }
                 for (; __builtin_expect(ok, 1) && n >= 2; n -= 2) {
-                    ok = step(1, mid, par0);
-                    if (__builtin_expect(ok, 1)) ok = step(1, mid, par1);
+                    ok = step(1, mid, par0, draw_next);
+                    if (__builtin_expect(ok, 1)) ok = step(1, mid, par1, draw_next);
                 }
-                if (ok && n == 1) ok = step(1, mid, par0);
+                if (ok && n == 1) ok = step(1, mid, par0, draw_next);
             }
-            if (ok) ok = step(L - 1, std::integral_constant<int, 2>(), rtpar);
+            if (ok) ok = step(L - 1, std::integral_constant<int, 2>(), rtpar, draw_next);
         }
         if (!ok) {  // an exchange timeout in one of the steps
             __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
