@@ -580,6 +580,26 @@ int mc_nuts_run_metric(const mc_program* prog, const mc_run_config* cfg,
                        void* workspace_dev, int64_t workspace_bytes, void* metric_dev,
                        int32_t adapt, void* hip_stream);
 
+/* The metric on the lane-resident NUTS kernel (opt-in; mc_nuts_run_metric and
+ * the default routing are unchanged).  mc_program_nuts_metric_lanes: 1 when
+ * mc_nuts_run with this max_tree_depth runs k_nuts_lr's register-only variant
+ * (mc_program_nuts_lanes == 2), else 0; -1 on a null program.
+ * mc_nuts_run_metric_lanes: mc_nuts_run_metric's arguments and validations,
+ * on k_nuts_lr<..., MET> (csrc/nuts_lanes.h): the same draws and decision
+ * rules as k_nuts with a metric (summation order differs as between the two
+ * kernels without one), a metric of ones gives mc_nuts_run's bits.
+ * MC_ERR_UNSUPPORTED, with the reason in mc_last_error, when the query above is
+ * not 1: the program is not planned as one lane-resident slice, it has
+ * broadcast parameters or scalar terms, or a parameter has more than one
+ * element.  No workspace is needed (one that is passed is forgotten as
+ * mc_nuts_run does); mc_debug_nuts_variant does not apply.  Asynchronous, no
+ * allocation.                                                               */
+int32_t mc_program_nuts_metric_lanes(const mc_program* prog, int32_t max_tree_depth);
+int mc_nuts_run_metric_lanes(const mc_program* prog, const mc_run_config* cfg,
+                             void* state_dev, float* samples_dev, const mc_trace* trace,
+                             void* workspace_dev, int64_t workspace_bytes, void* metric_dev,
+                             int32_t adapt, void* hip_stream);
+
 /* Random-walk Metropolis-Hastings (metropolis.py:6-101): per iteration
  * q' = q + f32(z * f32(proposal_scale)), z ~ N(0, I) (Philox, tag
  * MC_RNG_TAG_PROPOSAL), accept iff f32 log U < f32(lp(q') - lp(q)) (NaN

@@ -269,6 +269,25 @@ class ChainSet:
             ws.numel() if ws is not None else 0, _lib.ptr(self.metric), 1 if adapt else 0,
             _lib.stream_handle()))
 
+    def run_nuts_metric_lanes(self, *, adapt: bool = False, samples=None,
+                              trace: Optional[Trace] = None, **cfg):
+        """``run_nuts_metric`` on the lane-resident kernel (mc_nuts_run_metric_lanes:
+        register-only programs, EngineError(MC_ERR_UNSUPPORTED) otherwise)."""
+        if self.metric is None:
+            self.set_metric()
+        c = self._config(**cfg)
+        need = self.lib.mc_nuts_workspace_bytes(self.program.handle, self.C, c.max_tree_depth)
+        if need < 0:
+            raise _lib.EngineError(_lib.MC_ERR_UNSUPPORTED,
+                                   f"max_tree_depth {c.max_tree_depth} not supported")
+        ws = self._workspace(need)
+        tr = trace.c_struct() if trace is not None else None
+        _lib.check(self.lib.mc_nuts_run_metric_lanes(
+            self.program.handle, ctypes.byref(c), _lib.ptr(self.state), _lib.ptr(samples),
+            ctypes.byref(tr) if tr is not None else None, _lib.ptr(ws),
+            ws.numel() if ws is not None else 0, _lib.ptr(self.metric), 1 if adapt else 0,
+            _lib.stream_handle()))
+
 
 def torch_float32():
     import torch

@@ -262,6 +262,10 @@ SIGNATURES = [
     ("mc_nuts_run_metric", ctypes.c_int,
      [_VP, ctypes.POINTER(McRunConfig), _VP, _VP, ctypes.POINTER(McTrace), _VP,
       ctypes.c_int64, _VP, ctypes.c_int32, _VP]),
+    ("mc_program_nuts_metric_lanes", ctypes.c_int32, [_VP, ctypes.c_int32]),
+    ("mc_nuts_run_metric_lanes", ctypes.c_int,
+     [_VP, ctypes.POINTER(McRunConfig), _VP, _VP, ctypes.POINTER(McTrace), _VP,
+      ctypes.c_int64, _VP, ctypes.c_int32, _VP]),
     ("mc_mh_workspace_bytes", ctypes.c_int64, [_VP, ctypes.c_int64]),
     ("mc_mh_run", ctypes.c_int,
      [_VP, ctypes.POINTER(McRunConfig), ctypes.c_double, _VP, _VP, ctypes.POINTER(McTrace), _VP,

@@ -1340,6 +1340,14 @@ class Program:
         """True when mc_nuts_run runs k_nuts_lr's register-only variant."""
         return _lib.load().mc_program_nuts_lanes(self.handle, int(max_tree_depth)) == 2
 
+    def nuts_metric_lanes_why(self, max_tree_depth: int = 10) -> str:
+        """"" when mc_nuts_run_metric_lanes runs this program (the register-only
+        variant of k_nuts_lr), else the library's reason for declining it."""
+        lib = _lib.load()
+        if lib.mc_program_nuts_metric_lanes(self.handle, int(max_tree_depth)) == 1:
+            return ""
+        return (lib.mc_last_error() or b"").decode()
+
     @property
     def kernel_note(self) -> str:
         """Why HMC launches miss the lane-resident kernel ("" when they run it)."""

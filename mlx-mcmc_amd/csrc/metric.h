@@ -1,5 +1,6 @@
 // metric.h — per-chain diagonal mass matrix M = diag(1 / minv) of the
-// chain-per-workgroup samplers (k_hmc, k_nuts with MET) and its windowed
+// chain-per-workgroup samplers (k_hmc, k_nuts with MET) and of the register-only
+// lane-resident NUTS kernel (k_nuts_lr with MET, nuts_lanes.h), and its windowed
 // adaptation (Stan's scheme, per chain, inside the persistent kernel).
 //
 //   momentum   r_j = z_j * msqrt_j         msqrt_j = 1 / sqrt(minv_j), z as without a metric
@@ -81,12 +82,40 @@ __device__ __forceinline__ MetricDev metric_arg(const MetricDev& m) {
     return m;
 }
 
+// One element's share of a slow-phase warmup iteration: x enters the Welford
+// accumulator (mean, m2) as draw number nf of the window; at the window's last
+// iteration
+//   var = M2 / (n - 1),  minv = (n / (n + 5)) var + 1e-3 (5 / (n + 5))
+// replaces minv (a value that is not finite or not positive keeps the old one),
+// msqrt follows and the accumulator is reset.  Returns true when minv / msqrt
+// were replaced.  Shared by metric_adapt and the lane-resident k_nuts_lr.
+__device__ __forceinline__ bool metric_update_element(float x, float nf, bool last, float& mean,
+                                                      float& m2, float& minv, float& msqrt) {
+    float mu = mean;
+    const float d = x - mu;
+    mu = mu + d / nf;
+    const float s2 = m2 + d * (x - mu);
+    if (!last) {
+        mean = mu;
+        m2 = s2;
+        return false;
+    }
+    mean = 0.0f;
+    m2 = 0.0f;
+    const float var = s2 / (nf - 1.0f);
+    const float v = (nf / (nf + 5.0f)) * var + 1e-3f * (5.0f / (nf + 5.0f));
+    if (v > 0.0f && v < __builtin_inff()) {
+        minv = v;
+        msqrt = 1.0f / sqrtf(v);
+        return true;
+    }
+    return false;
+}
+
 // One warmup iteration's adaptation work of chain c, after its accept / reject
 // (q: the chain's current position; element j belongs to thread j % T).  In the
-// slow phase q enters the Welford accumulator; at a window's last iteration
-//   var = M2 / (n - 1),  minv = (n / (n + 5)) var + 1e-3 (5 / (n + 5))
-// replaces minv (an element whose new value is not finite or not positive
-// keeps its old one), msqrt follows and the accumulator is reset.  minv / msqrt
+// slow phase q enters the Welford accumulator; at a window's last iteration the
+// metric is replaced (metric_update_element).  minv / msqrt
 // are the kernel's working copies (LDS or the buffer).  Returns true (for every
 // thread of the group) when the metric was updated; the caller synchronises
 // the group before the next momentum draw.
@@ -102,29 +131,17 @@ __device__ __forceinline__ bool metric_adapt(const MetricDev& M, MetricScalars& 
     float* mean = M.mean + c * D;
     float* m2 = M.m2 + c * D;
     for (int j = tid; j < D; j += T) {
-        const float x = q[j];
-        float mu = mean[j];
-        const float d = x - mu;
-        mu = mu + d / nf;
-        const float s2 = m2[j] + d * (x - mu);
-        if (!last) {
-            mean[j] = mu;
-            m2[j] = s2;
-        } else {
-            const float var = s2 / (nf - 1.0f);
-            const float v = (nf / (nf + 5.0f)) * var + 1e-3f * (5.0f / (nf + 5.0f));
-            if (v > 0.0f && v < __builtin_inff()) {
-                const float sq = 1.0f / sqrtf(v);
-                minv[j] = v;
-                msqrt[j] = sq;
-                if (M.in_lds) {
-                    M.minv[c * D + j] = v;
-                    M.msqrt[c * D + j] = sq;
-                }
+        float mu = mean[j], s2 = m2[j], v = 0.0f, sq = 0.0f;  // (v, sq: set when replaced)
+        if (metric_update_element(q[j], nf, last, mu, s2, v, sq)) {
+            minv[j] = v;
+            msqrt[j] = sq;
+            if (M.in_lds) {
+                M.minv[c * D + j] = v;
+                M.msqrt[c * D + j] = sq;
             }
-            mean[j] = 0.0f;
-            m2[j] = 0.0f;
         }
+        mean[j] = mu;
+        m2[j] = s2;
     }
     if (last) {
         ms.n_window = 0;

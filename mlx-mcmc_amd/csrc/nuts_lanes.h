@@ -54,11 +54,21 @@ __host__ __device__ constexpr int64_t nuts_lr_draw_words(int max_depth) {
 // 2^MAXJ words and the flags), the chain's wave reads each with one LDS
 // load instead of a scalar Philox (~100 SALU) in its leaf's issue stream.
 // The same draws, so the same trees.
-template <int RS, int NSH, int SPEC, bool PW = false>
+// MET (off by default, register-only programs; the instantiations without it
+// are unchanged): k_nuts' per-chain diagonal metric (metric.h, nuts.h MET), one
+// trailing MetricDev argument.  Each lane keeps minv / msqrt of its parameters
+// in registers (1.0f in a slot without one): momentum z * msqrt, drift and
+// kinetic energy through the velocity minv * r, the U-turn test and the arena
+// on (q, r) as they are.  During warmup the leader lane of each parameter runs
+// metric_update_element on the current sample with mean / M2 in the metric
+// buffer; at an update dual averaging restarts as in k_nuts.
+template <int RS, int NSH, int SPEC, bool PW = false, bool MET = false, typename... MArg>
 __global__ void __launch_bounds__(PW ? 128 : 64)
 k_nuts_lr(LrCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, float* samples,
-          TraceDev tr) {
+          TraceDev tr, MArg... met) {
     static_assert(NSH <= kLrMaxShared, "shared parameters");
+    static_assert(sizeof...(MArg) == (MET ? 1 : 0), "MET takes one MetricDev argument");
+    static_assert(!MET || SPEC == 2, "the metric runs on the register-only variant");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const mc_run_config& cfg = A.cfg;
     const int j = threadIdx.x & 63;  // lane
@@ -254,6 +264,20 @@ k_nuts_lr(LrCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, 
         Cg[r] = gk[r] >= 0 ? st_g[c * D + gk[r]] : 0.0f;
     }
     float Cqs = xon ? st_q[c * D + xg] : 1.0f, Cgs = xon ? st_g[c * D + xg] : 0.0f;
+
+    // MET: minv / msqrt of this lane's parameters (every lane of a replicated
+    // parameter's group carries the same values) and the chain's metric scalars
+    const MetricDev M = metric_arg<MET>(met...);
+    [[maybe_unused]] float mnv[RS], msq[RS];
+    [[maybe_unused]] MetricScalars ms = {};
+    if constexpr (MET) {
+#pragma unroll
+        for (int r = 0; r < RS; ++r) {
+            mnv[r] = gk[r] >= 0 ? M.minv[c * D + gk[r]] : 1.0f;
+            msq[r] = gk[r] >= 0 ? M.msqrt[c * D + gk[r]] : 1.0f;
+        }
+        ms = M.sc[c];
+    }
 
     // the log density and gradient at (R.q, sh.q): R.g, sh.g; returns log p
     LrPriv<RS> R;
@@ -490,7 +514,10 @@ k_nuts_lr(LrCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, 
             const float z = gk[r] >= 0 ? normal_of(gk[r]) : 0.0f;
             EM.q[r] = EP.q[r] = Cq[r];
             EM.g[r] = EP.g[r] = Cg[r];
-            EM.p[r] = EP.p[r] = z;
+            if constexpr (MET)
+                EM.p[r] = EP.p[r] = z * msq[r];
+            else
+                EM.p[r] = EP.p[r] = z;
         }
         {
             const float z = xon ? normal_of(xg) : 0.0f;
@@ -502,8 +529,13 @@ k_nuts_lr(LrCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, 
         {
             float k = 0.0f;
 #pragma unroll
-            for (int r = 0; r < RS; ++r)
-                if (lead) k += EM.p[r] * EM.p[r];
+            for (int r = 0; r < RS; ++r) {
+                if constexpr (MET) {
+                    if (lead) k += EM.p[r] * (mnv[r] * EM.p[r]);
+                } else {
+                    if (lead) k += EM.p[r] * EM.p[r];
+                }
+            }
             if (xone) k += Mrs * Mrs;
             K0 = wave_sum(k);
         }
@@ -621,7 +653,11 @@ k_nuts_lr(LrCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, 
 #pragma unroll
                 for (int r = 0; r < RS; ++r) {
                     const f2 pj = (f2){R.p[r][0], R.p[r][1]} + f2s(h) * (f2){R.g[r][0], R.g[r][1]};
-                    const f2 qj = (f2){R.q[r][0], R.q[r][1]} + f2s(e) * pj;
+                    f2 qj;
+                    if constexpr (MET)  // drift along the velocity minv * r
+                        qj = (f2){R.q[r][0], R.q[r][1]} + f2s(e) * (f2s(mnv[r]) * pj);
+                    else
+                        qj = (f2){R.q[r][0], R.q[r][1]} + f2s(e) * pj;
                     R.p[r][0] = pj[0];
                     R.p[r][1] = pj[1];
                     R.q[r][0] = qj[0];
@@ -650,7 +686,11 @@ k_nuts_lr(LrCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, 
                             (f2){R.p[r][0], R.p[r][1]} + f2s(h) * (f2){R.g[r][0], R.g[r][1]};
                         R.p[r][0] = pj[0];
                         R.p[r][1] = pj[1];
-                        if (lead) k += R.p[r][0] * R.p[r][0];
+                        if constexpr (MET) {
+                            if (lead) k += R.p[r][0] * (mnv[r] * R.p[r][0]);
+                        } else {
+                            if (lead) k += R.p[r][0] * R.p[r][0];
+                        }
                     }
                     float ws[2] = {lane_lp, k};
                     wave_sum2(ws);
@@ -831,7 +871,8 @@ k_nuts_lr(LrCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, 
         sc.n_total += 1;
         sc.depth_sum += jd;
         if (warm && cfg.adapt_step_size) {  // dual averaging, nuts.py:299-310
-            const double m = (double)it;
+            double m = (double)it;
+            if constexpr (MET) m = (double)(it - ms.da_origin);
             const double eta = 1.0 / (m + 10.0);
             sc.h_bar = (1.0 - eta) * sc.h_bar + eta * (cfg.target_accept - alpha);
             const float lf = sc.mu - (float)(sqrt(m + 1.0) / 0.05 * sc.h_bar);
@@ -842,6 +883,47 @@ k_nuts_lr(LrCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, 
             const double m_eta = pow(m + 1.0, -0.75);
             const double lb = m_eta * log(eps) + (1.0 - m_eta) * log(sc.step_size_bar);
             sc.step_size_bar = (double)mc_expf_ref((float)lb);
+        }
+        if constexpr (MET) {
+            // windowed adaptation (metric.h metric_adapt, per lane): the current
+            // sample enters the window's accumulator in the metric buffer (read
+            // and written here only, never live across the tree walk).  Every
+            // lane of a replicated parameter's group computes the same update
+            // from the same loads, so its registers follow; the leader stores.
+            if (warm && M.adapt) {
+                const MetricSchedule sch = metric_schedule(cfg.num_warmup);
+                if (metric_slow_phase(sch, cfg.num_warmup, it)) {
+                    ms.n_window += 1;
+                    const float nf = (float)ms.n_window;
+                    const bool last = it + 1 == metric_window_end(sch, cfg.num_warmup, it);
+#pragma unroll
+                    for (int r = 0; r < RS; ++r) {
+                        if (gk[r] < 0) continue;
+                        const int64_t o = c * D + gk[r];
+                        float mu = M.mean[o], s2 = M.m2[o];
+                        const bool upd =
+                            metric_update_element(Cq[r], nf, last, mu, s2, mnv[r], msq[r]);
+                        if (lead) {
+                            M.mean[o] = mu;
+                            M.m2[o] = s2;
+                            if (upd) {
+                                M.minv[o] = mnv[r];
+                                M.msqrt[o] = msq[r];
+                            }
+                        }
+                    }
+                    if (last) {
+                        ms.n_window = 0;
+                        ms.n_updates += 1;
+                        if (cfg.adapt_step_size) {  // dual averaging restarts (nuts.h)
+                            sc.mu = mc_logf_ref((float)(10.0 * eps));
+                            sc.h_bar = 0.0;
+                            sc.step_size_bar = 1.0;
+                            ms.da_origin = it + 1;
+                        }
+                    }
+                }
+            }
         }
         if (!warm && samples != nullptr) {
             const int64_t si = it - cfg.num_warmup - cfg.sample_begin;
@@ -888,6 +970,7 @@ k_nuts_lr(LrCtx P, RunArgs A, mc_chain_scalars* scal, float* st_q, float* st_g, 
         sc.step_size = eps;
         sc.n_grad += n_grad;
         scal[c] = sc;
+        if constexpr (MET) M.sc[c] = ms;
     }
 }
 

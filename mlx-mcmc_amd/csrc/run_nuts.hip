@@ -1,5 +1,6 @@
 // run_nuts.hip — NUTS launches (k_nuts_lr, k_nuts) and mc_nuts_run.
 #include "run_nuts_sl.h"
+#include "run_nuts_lr_met.h"
 #include "jit.h"
 
 
@@ -113,17 +114,25 @@ static bool use_nuts_lanes(const mc_program* p, int max_depth) {
 // no broadcast parameter, no scalar term and one slice term with at most one
 // element per (lane, slot): a data-scale term or a direct term with constant
 // loc and scale (k_nuts_lr<..., 2>: the gradient from per-slot registers)
-static bool lanes_register_only(const mc_program* p) {
+// (nullptr when it is, else which condition fails)
+static const char* lanes_register_only_why(const mc_program* p) {
     const LanePlan& L = p->lr;
-    if (!L.ok || L.S != 1 || L.Dsh != 0 || !L.sterms.empty() || L.blocks[2] != 1) return false;
+    if (!L.ok || L.S != 1) return "the program is not planned as one lane-resident slice";
+    if (L.Dsh != 0 || !L.sterms.empty())
+        return "the program has broadcast parameters or scalar terms";
+    if (L.blocks[2] != 1) return "the program has more than one slice term";
     const LrTerm& T = L.terms[0];
     const bool ds = T.sig == LS_DSCALE && T.kind[1 - T.pp] != SK_SHARED;
     const bool dir = T.sig == LS_PP_C_C && T.pp == 0;
-    if (!ds && !dir) return false;
+    if (!ds && !dir)
+        return "the slice term is not a Normal with a data or constant scale on the parameter";
     const int32_t* lens = (const int32_t*)&L.data[(size_t)L.blocks[0] + T.len_off];
     for (int i = 0; i < T.nslot * 64; ++i)
-        if (lens[i] > 1) return false;
-    return true;
+        if (lens[i] > 1) return "a parameter has more than one element";
+    return nullptr;
+}
+static bool lanes_register_only(const mc_program* p) {
+    return lanes_register_only_why(p) == nullptr;
 }
 
 extern "C" int32_t mc_program_nuts_lanes(const mc_program* p, int32_t max_tree_depth) {
@@ -262,6 +271,53 @@ extern "C" int mc_nuts_run_metric(const mc_program* p, const mc_run_config* cfg,
         return launch_nuts<decltype(W)::value, decltype(L)::value, decltype(E)::value, true>(
             p, cfg, state, samples, tr, w, st, metric, adapt);
     });
+}
+
+// Why mc_nuts_run_metric_lanes declines this program (nullptr: it runs it)
+static const char* nuts_metric_lanes_why(const mc_program* p, int32_t max_depth) {
+    if (use_nuts_sliced(p, max_depth) || !use_nuts_lanes(p, max_depth))
+        return "the program is not planned as one lane-resident slice";
+    return lanes_register_only_why(p);
+}
+static int nuts_metric_lanes_refuse(const char* why) {
+    return fail(MC_ERR_UNSUPPORTED,
+                "the metric on the lane-resident kernel takes register-only programs and %s: "
+                "mc_nuts_run_metric runs it on k_nuts (mc_program_set_slices(prog, 1))", why);
+}
+
+// (0: the reason is left in mc_last_error)
+extern "C" int32_t mc_program_nuts_metric_lanes(const mc_program* p, int32_t max_tree_depth) {
+    if (!p) return -1;
+    const char* why = nuts_metric_lanes_why(p, max_tree_depth);
+    if (why == nullptr) return 1;
+    nuts_metric_lanes_refuse(why);
+    return 0;
+}
+
+extern "C" int mc_nuts_run_metric_lanes(const mc_program* p, const mc_run_config* cfg, void* state,
+                                        float* samples, const mc_trace* tr, void* ws,
+                                        int64_t ws_bytes, void* metric, int32_t adapt,
+                                        void* stream) {
+    int rc = check_cfg(p, cfg, state);
+    if (rc) return rc;
+    if (!metric) return fail(MC_ERR_INVALID, "metric buffer is NULL");
+    if (cfg->max_tree_depth < 0 || cfg->max_tree_depth > kMaxTreeDepth)
+        return fail(MC_ERR_UNSUPPORTED, "max_tree_depth must be in [0, %d]", kMaxTreeDepth);
+    if (const char* why = nuts_metric_lanes_why(p, cfg->max_tree_depth))
+        return nuts_metric_lanes_refuse(why);
+    if (cfg->num_chains == 0 || cfg->iter_count == 0) return MC_OK;
+    // (mc_nuts_run's contract: what mc_nuts_workspace_bytes asks for, unused here)
+    const int64_t need = mc_nuts_workspace_bytes(p, cfg->num_chains, cfg->max_tree_depth);
+    if (need > 0 && (ws == nullptr || ws_bytes < need))
+        return fail(MC_ERR_INVALID, "workspace too small: need %lld bytes", (long long)need);
+    if (ws) ws_forget(ws);
+    // LDS and the draw wave as launch_nuts_lr decides them
+    const size_t lds = nuts_lr_lds_bytes(p, cfg->max_tree_depth);
+    const size_t lds_pw = lds + (size_t)nuts_lr_draw_words(cfg->max_tree_depth) * 4;
+    const bool pw = nuts_draw_wave_enabled() && cfg->max_tree_depth <= 12 &&
+                    lds_pw <= (size_t)kSlLdsBudget;
+    return nuts_lr_met_launch(p, cfg, state, samples, tr, metric, adapt, pw ? lds_pw : lds, pw,
+                              (hipStream_t)stream);
 }
 
 #ifdef MC_STAMPS

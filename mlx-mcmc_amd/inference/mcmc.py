@@ -2,7 +2,9 @@
 
 ``MCMC(log_prob_fn).run(...)`` dispatches ``method='hmc'`` / ``'nuts'`` to
 the MI355X kernels exactly as the reference's branches do (mcmc.py:83-133):
-``key`` is built from ``random_seed``, extra kwargs go to the sampler,
+``key`` is built from ``random_seed``, extra kwargs go to the sampler
+(``inverse_mass_matrix``, ``adapt_mass_matrix`` and, for ``'nuts'``,
+``nuts_kernel`` among them),
 samples are stored as NumPy arrays in ``.samples`` and the rate in
 ``.acceptance_rate``.  ``summary`` / ``print_summary`` follow mcmc.py:191-246,
 computed on the device from the kept [C, S, D] sample buffer

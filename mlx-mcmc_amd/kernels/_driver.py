@@ -92,7 +92,7 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
                 progress_every: Optional[int] = None, return_trace: bool = False,
                 keep_on_device: bool = False, initial_positions=None, num_slices: int = 0,
                 slice_kernel: str = "auto", inverse_mass_matrix=None,
-                adapt_mass_matrix: bool = False):
+                adapt_mass_matrix: bool = False, nuts_kernel: str = "auto"):
     import torch
 
     if algorithm not in ("hmc", "nuts"):
@@ -104,11 +104,16 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
     if C < 1:
         raise ValueError("num_chains must be >= 1")
     # a diagonal metric (csrc/metric.h) runs on the chain-per-workgroup tape
-    # kernels only: the program is planned as num_slices=1 / nuts_kernel="tape"
+    # kernels: the program is planned as num_slices=1 / nuts_kernel="tape" —
+    # unless nuts(nuts_kernel="lanes") asks for the lane-resident kernel
+    # (k_nuts_lr's register-only variant, csrc/nuts_lanes.h MET): then the
+    # automatic plan stands and a program that variant does not take is an error
     use_metric = inverse_mass_matrix is not None or bool(adapt_mass_matrix)
+    # (nuts() takes "lanes" with a metric only)
+    metric_lanes = use_metric and algorithm == "nuts" and nuts_kernel == "lanes"
     minv0 = (_metric_array(inverse_mass_matrix, initial_params, C)
              if inverse_mass_matrix is not None else None)
-    if use_metric:
+    if use_metric and not metric_lanes:
         if num_slices > 1 or slice_kernel != "auto":
             raise ValueError("a mass matrix runs on the chain-per-workgroup kernels: leave "
                              "num_slices at 0 or 1 and slice_kernel at 'auto'")
@@ -119,6 +124,11 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
         # a large regression's affine terms as expression terms: the sliced
         # NUTS kernel instead of the tape (_trace.nuts_program)
         program = _trace.nuts_program(program, max_tree_depth)
+    if metric_lanes:
+        why = program.nuts_metric_lanes_why(max_tree_depth)
+        if why:
+            raise ValueError(f"nuts_kernel='lanes' with a mass matrix: {why}. The default "
+                             "nuts_kernel runs the metric on the tape kernel k_nuts")
     layout = program.layout
     note = program.kernel_note
     # no warning where the user cannot act on it: no lane-resident kernel
@@ -156,7 +166,9 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
         cfg["slice_mode"] = {"reference": 0, "exact": 1}[slice_mode]
         launch = chains.run_nuts
         if use_metric:
-            launch = functools.partial(chains.run_nuts_metric, adapt=bool(adapt_mass_matrix))
+            launch = functools.partial(
+                chains.run_nuts_metric_lanes if metric_lanes else chains.run_nuts_metric,
+                adapt=bool(adapt_mass_matrix))
         every = progress_every or 250
     out = (lambda *a: print(*a)) if progress else (lambda *a: None)
 
@@ -244,9 +256,10 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
                             else program.slice_kernel)
     if note and algorithm == "hmc":
         info.extra["kernel_note"] = note
-    if use_metric:
+    if use_metric and not metric_lanes:
         info.extra["kernel_note"] = ("a mass matrix runs on the chain-per-workgroup tape kernel "
                                      f"(k_{algorithm}), as num_slices=1 does")
+    if use_metric:
         info.extra["inverse_mass_matrix"] = chains.inverse_mass().cpu().numpy()
         info.extra["metric_updates"] = chains.metric_scalars()["n_updates"].copy()
     host = flat.cpu().numpy()

@@ -13,8 +13,11 @@ one chain per chain group on the gradient tape), or ``k_nuts_sl``
 model plans as one lane-resident slice, the sliced kernel ``k_nuts_sl``
 (csrc/nuts_sliced.h: one wave per chain and data slice, one record exchange
 per leaf) when it plans as several fast-form slices (the README "Large"
-row), else ``k_nuts``; "tape" keeps ``k_nuts``.  ``num_slices``: data slices
-per chain (0: the automatic plan, as ``hmc()``).
+row), else ``k_nuts``; "tape" keeps ``k_nuts``; "lanes" is accepted with a mass
+matrix only (below: the metric on ``k_nuts_lr``, or a ``ValueError``) — without one
+it raises ``ValueError`` before anything is traced, as an unknown value does
+("auto" already picks ``k_nuts_lr`` where the model plans onto it).
+``num_slices``: data slices per chain (0: the automatic plan, as ``hmc()``).
 
 ``slice_mode="reference"`` (default) reproduces the reference's float32
 slice variable: u = f32 exp(log u) rounds to the smallest denormal (log u =
@@ -25,6 +28,10 @@ Keyword-only additions as for ``hmc()``, ``inverse_mass_matrix`` and
 ``adapt_mass_matrix`` among them: a per-chain diagonal metric, adapted during
 warmup in Stan's windows with dual averaging restarted at each update
 (csrc/metric.h); such a run takes ``k_nuts`` as ``nuts_kernel="tape"`` does.
+``nuts_kernel="lanes"`` opts such a run onto ``k_nuts_lr`` instead (several times
+the leaf rate) when the model is register-only — no shared parameter, no scalar
+term, one Normal term with one element per parameter (theta_i ~ N(m, s_i)); any
+other model raises ``ValueError`` before a launch and keeps the default route.
 (On a model with constrained parameters the restart's first, ~15x longer step
 can meet the reference's NaN -> alpha = 1 rule and run the step size away —
 DESIGN section 4; adapt with ``adapt_step_size=False``, or pass a metric adapted
@@ -49,8 +56,13 @@ def nuts(log_prob_fn, initial_params, num_samples=1000, num_warmup=1000, step_si
     is the fraction of sampling iterations whose mean acceptance statistic
     exceeds 0.5 (nuts.py:347).
     """
-    if nuts_kernel not in ("auto", "tape"):
-        raise ValueError(f"nuts_kernel must be 'auto' or 'tape', not {nuts_kernel!r}")
+    if nuts_kernel not in ("auto", "tape", "lanes"):
+        raise ValueError(f"nuts_kernel must be 'auto', 'tape' or 'lanes', not {nuts_kernel!r}")
+    if nuts_kernel == "lanes" and inverse_mass_matrix is None and not adapt_mass_matrix:
+        raise ValueError("nuts_kernel='lanes' chooses the kernel of a run with a mass matrix: "
+                         "pass inverse_mass_matrix= or adapt_mass_matrix=True with it. Without "
+                         "one, nuts_kernel='auto' already runs the lane-resident kernel "
+                         "wherever the model plans onto it")
     samples, rate, info = run_sampler(
         "nuts", log_prob_fn, initial_params, num_samples=num_samples, num_warmup=num_warmup,
         step_size=step_size, target_accept=target_accept, adapt_step_size=adapt_step_size,
@@ -59,7 +71,8 @@ def nuts(log_prob_fn, initial_params, num_samples=1000, num_warmup=1000, step_si
         return_trace=return_trace, keep_on_device=keep_on_device,
         initial_positions=initial_positions,
         num_slices=1 if nuts_kernel == "tape" else int(num_slices),
-        inverse_mass_matrix=inverse_mass_matrix, adapt_mass_matrix=adapt_mass_matrix)
+        inverse_mass_matrix=inverse_mass_matrix, adapt_mass_matrix=adapt_mass_matrix,
+        nuts_kernel=nuts_kernel)
     if return_info:
         return samples, rate, info
     return samples, rate

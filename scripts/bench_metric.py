@@ -7,10 +7,16 @@ Two models, 64 chains each: the kappa = 1000 Gaussian of the NUTS bench
   default        identity metric on the kernel the model gets today
   tape_identity  identity metric on the chain-per-workgroup tape (k_nuts)
   tape_adapted   the metric adapted during warmup, on the tape
+  lanes_adapted  the metric adapted during warmup, on the lane-resident kernel
+                 (k_nuts_lr with MET, mc_nuts_run_metric_lanes)
+  lanes_ones     that kernel with a metric of ones, not adapted: the draws of
+                 `default`, so its leaf rate against `default`'s is the price
+                 of the metric's multiplies and registers on the leaf path
 
-The three variants are interleaved, round after round on one device, and every
-variant reports the median over the rounds of: mean tree depth, leaf-steps/s of
-the timed sampling phase, and the minimum / median over the parameters of
+The last two run on the Gaussian only (the hierarchical model has shared
+parameters: not register-only).  The variants are interleaved, round after
+round on one device, and every variant reports the median over the rounds of:
+mean tree depth, leaf-steps/s of the timed sampling phase, and the minimum / median over the parameters of
 ESS/s (reference compute_ess per chain and parameter, summed over chains,
 divided by the sampling time).  Every run is the same seed: the rounds differ
 in timing only.
@@ -29,6 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 VARIANTS = ("default", "tape_identity", "tape_adapted")
+LANES_VARIANTS = ("lanes_adapted", "lanes_ones")
 
 
 def one_run(prog, variant, init, eps0, C, Wm, K, depth, slice_mode, seed):
@@ -44,7 +51,8 @@ def one_run(prog, variant, init, eps0, C, Wm, K, depth, slice_mode, seed):
         launch = chains.run_nuts
     else:
         chains.set_metric()
-        launch = lambda **kw: chains.run_nuts_metric(adapt=variant == "tape_adapted", **kw)  # noqa: E731
+        run = chains.run_nuts_metric_lanes if variant in LANES_VARIANTS else chains.run_nuts_metric
+        launch = lambda **kw: run(adapt=variant.endswith("_adapted"), **kw)  # noqa: E731
     launch(iter_begin=0, iter_count=Wm, **cfg)
     torch.cuda.synchronize()
     g0 = chains.scalars()["n_grad"].astype(np.int64)
@@ -88,23 +96,27 @@ def main():
     for name, ((lp, init), eps0, slice_mode) in cases.items():
         progs = {"default": _trace.compile_model(lp, init)}
         progs["tape_identity"] = progs["tape_adapted"] = _trace.compile_model(lp, init, slices=1)
-        runs = {v: [] for v in VARIANTS}
+        variants = VARIANTS
+        if progs["default"].nuts_metric_lanes_why(10) == "":
+            variants = VARIANTS + LANES_VARIANTS
+            progs.update({v: progs["default"] for v in LANES_VARIANTS})
+        runs = {v: [] for v in variants}
         for r in range(args.rounds + 1):                    # round 0 warms clocks and caches
-            for v in VARIANTS:
+            for v in variants:
                 res = one_run(progs[v], v, init, eps0, args.chains, args.warmup, args.samples, 10,
                               slice_mode, seed=0)
                 if r > 0:
                     runs[v].append(res)
         out = {"model": name, "chains": args.chains, "num_warmup": args.warmup,
                "num_samples": args.samples, "rounds": args.rounds, "max_tree_depth": 10,
-               "kernels": {v: progs[v].nuts_kernel(10) for v in VARIANTS}, "variants": {}}
-        for v in VARIANTS:
+               "kernels": {v: progs[v].nuts_kernel(10) for v in variants}, "variants": {}}
+        for v in variants:
             keys = [k for k in runs[v][0] if k != "finite"]
             out["variants"][v] = {k: float(np.median([x[k] for x in runs[v]])) for k in keys}
             out["variants"][v]["finite"] = all(x["finite"] for x in runs[v])
             out["variants"][v]["seconds_all"] = [x["seconds"] for x in runs[v]]
         base = out["variants"]["default"]
-        for v in VARIANTS:
+        for v in variants:
             out["variants"][v]["ess_per_s_min_vs_default"] = (
                 out["variants"][v]["ess_per_s_min"] / base["ess_per_s_min"])
         print(json.dumps(out), flush=True)
