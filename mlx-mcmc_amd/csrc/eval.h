@@ -828,8 +828,13 @@ enum : uint32_t {
 // sequence (v_div_scale / v_div_fmas / v_div_fixup).  An element loop's
 // uniform divisor keeps its reciprocal in a register.  v_div_fixup_f32
 // replaces the quotient by the IEEE result where an operand is special (a
-// zero or infinite divisor, infinite or NaN operands).  Divisors beyond 2^126
-// in magnitude (their reciprocal is subnormal) are outside its range.
+// zero or infinite divisor, infinite or NaN operands).  Two kinds of divisor
+// are outside its range (pinned by tests/test_gpu_expr_ops.py
+// test_div_outside_its_range): beyond 2^126 in magnitude the reciprocal is
+// subnormal and the unit returns 0, so the quotient comes out 0; a subnormal
+// divisor's reciprocal overflows, and a non-zero dividend gives +-inf.
+// Inside the range the quotient is within an ulp (0.5 ulp measured over the
+// tests' bulk sweep).
 MC_DEV float ex_div(float x, float y) {
     const float r = __builtin_amdgcn_rcpf(y);
     const float q = x * r;
@@ -844,7 +849,8 @@ MC_DEV float ex_div(float x, float y) {
 //   exp: t = x log2(e) rounded, its residual x log2(e) - t from an FMA plus
 //        the low part of log2(e); exp2(t) (1 + residual ln 2).  Infinite or
 //        zero exp2(t) (|x| beyond the range, +-inf) is returned as is.
-//        Subnormal results are the unit's.
+//        The unit flushes subnormal results: exp(x) is 0 below
+//        log(FLT_MIN) = -87.3365.
 //   log: log2 of the argument (a subnormal one scaled by 2^32 first) times
 //        ln 2; 0 -> -inf, negative -> NaN, inf -> inf.
 MC_DEV float ex_exp(float x) {
@@ -863,14 +869,15 @@ MC_DEV float ex_log(float x) {
 }
 
 // log(1 + x) from the rounded sum u = 1 + x: log(u) * (x / (u - 1))
-// (the quotient corrects the rounding of u; exact for u - 1 == x), x where
-// u rounds to 1, and log(u) for u = inf.  A few ulp, branch-free, against
-// log1pf's ~40 instructions.
+// (the quotient corrects the rounding of u; it is 1 for u - 1 == x and is
+// then left out, which also keeps u beyond 2^126 away from ex_div's range
+// limit and covers u = inf), x where u rounds to 1.  A few ulp (2.8 measured),
+// branch-free, against log1pf's ~40 instructions.
 MC_DEV float ex_log1p(float x) {
     const float u = 1.0f + x;
     const float d = u - 1.0f;
     const float l = ex_log(u);
-    const float r = __builtin_isinf(u) ? l : l * ex_div(x, d);
+    const float r = d == x ? l : l * ex_div(x, d);
     return d == 0.0f ? x : r;
 }
 
@@ -1091,8 +1098,8 @@ MC_DEV exf2 ex2_log1p(exf2 x) {
     const exf2 d = u - 1.0f;
     const exf2 l = ex2_log(u);
     const exf2 r = l * ex2_div(x, d);
-    return exf2{d.x == 0.0f ? x.x : (__builtin_isinf(u.x) ? l.x : r.x),
-                d.y == 0.0f ? x.y : (__builtin_isinf(u.y) ? l.y : r.y)};
+    return exf2{d.x == 0.0f ? x.x : (d.x == x.x ? l.x : r.x),
+                d.y == 0.0f ? x.y : (d.y == x.y ? l.y : r.y)};
 }
 MC_DEV exf2 ex2_each(float (*f)(float), exf2 x) { return exf2{f(x.x), f(x.y)}; }
 // ex_normal's operations on a pair (every component rounds as the scalar

@@ -6,6 +6,7 @@ import ctypes
 
 import numpy as np
 
+import _expr_ops
 import workloads as W
 
 
@@ -28,7 +29,12 @@ MODELS = {"two_predictor": W.two_predictor_regression,
           "huber": W.huber_regression,
           "weighted_indexed": W.weighted_indexed,
           "tempered": W.tempered,
-          "tiny_scalar": tiny_scalar}
+          "tiny_scalar": tiny_scalar,
+          # every expression op as a node, in three models (tests/_expr_ops.py;
+          # 96 elements: the automatic plan keeps them on the tape kernels)
+          **{g: _expr_ops.group_model(g, _expr_ops.N_TAPE) for g in _expr_ops.GROUPS},
+          # exp / sigmoid / log1p at large arguments on the tape JIT's pair code
+          "ops_pairs": _expr_ops.group_model("ops_pairs", _expr_ops.N_GROUP)}
 
 
 def host_program(lp, init):
