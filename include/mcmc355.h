@@ -492,6 +492,15 @@ int mc_debug_lane_plan_host(mc_program* prog, int32_t num_slices);
  * in mc_last_error) when only the lane planner declines.                    */
 int mc_debug_plan_digest(mc_program* prog, int32_t num_slices, uint64_t* out, int32_t n_out);
 int64_t mc_debug_expr_jit_lane_source(const mc_program* prog, char* buf, int64_t cap);
+/* Test hook (host tables, also of a host-only program): the tape plan of term
+ * `term` in evaluation order (wave tasks last, csrc/program.hip), ten values,
+ * n_out >= 10: dist, n (clamped to INT32_MAX), primary (-1 strided, else the
+ * operand slot of the non-injective gather), npass, pass_masks (4 bits per
+ * pass: 1 value, 2 loc, 4 scale, 8 log p), wave_task (-1 or the wave), ncomb
+ * (> 0: split runs, the groups combined), ntiles, nvirt, sync_before.
+ * MC_ERR_INVALID for a null program or buffer, n_out < 10 or a term out of
+ * range.  Changes nothing.                                                  */
+int mc_debug_term_plan(const mc_program* prog, int32_t term, int32_t* out, int32_t n_out);
 /* Test hooks (host code, no device): the samplers' Box-Muller pair from two
  * Philox words per pair (words [n][2] -> out [n][2] f32) and their f32 log
  * of a uniform in (0, 1] (philox.h mc_box_muller / mc_logf_unit).         */

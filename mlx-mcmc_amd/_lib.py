@@ -241,6 +241,8 @@ SIGNATURES = [
     ("mc_debug_plan_digest", ctypes.c_int,
      [_VP, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
     ("mc_debug_expr_jit_lane_source", ctypes.c_int64, [_VP, ctypes.c_char_p, ctypes.c_int64]),
+    ("mc_debug_term_plan", ctypes.c_int,
+     [_VP, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     ("mc_box_muller_host", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     ("mc_logf_unit_host", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     ("mc_hmc_run", ctypes.c_int,

@@ -1144,3 +1144,18 @@ extern "C" int mc_program_destroy(mc_program* p) {
 
 extern "C" int32_t mc_program_num_params(const mc_program* p) { return p ? p->D : -1; }
 extern "C" int32_t mc_program_waves_per_chain(const mc_program* p) { return p ? p->wpc : -1; }
+
+// Test hook: the tape plan of one term, in evaluation order (host tables).
+extern "C" int mc_debug_term_plan(const mc_program* p, int32_t term, int32_t* out, int32_t n_out) {
+    if (!p) return fail(MC_ERR_INVALID, "program is NULL");
+    if (!out || n_out < 10) return fail(MC_ERR_INVALID, "out holds 10 values");
+    if (term < 0 || (size_t)term >= p->terms.size())
+        return fail(MC_ERR_INVALID, "term %d out of range (the program has %zu)", term,
+                    p->terms.size());
+    const DevTerm& T = p->terms[term];
+    const int32_t v[10] = {T.dist, (int32_t)std::min<int64_t>(T.n, INT32_MAX), T.primary, T.npass,
+                           (int32_t)T.pass_masks, T.wave_task, T.ncomb, T.ntiles, T.nvirt,
+                           T.sync_before};
+    std::copy(v, v + 10, out);
+    return MC_OK;
+}
