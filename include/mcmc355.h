@@ -684,6 +684,56 @@ int mc_select(int64_t C, int64_t S, int64_t D, const float* samples_dev,
               float* out_dev, void* workspace_dev, int64_t workspace_bytes,
               void* hip_stream);
 
+/* ---- pointwise log-likelihood over kept draws (no reference code: its README
+ * roadmap lists "Model comparison (WAIC, LOO)") ------------------------------
+ * The likelihood is a program of its own, traced like log_prob.  Every element
+ * of every term is one observation: M = sum_t n_t, term by term in the order
+ * the caller passed them and inside a term in the caller's element order.  The
+ * pointwise value of element i of term t under a draw q is
+ *     x = weight_t * lp_{t,i}(q)                (one f32 product)
+ * with lp the tape's per-element f32 arithmetic (csrc/eval.h elem_eval and, for
+ * expression terms, ex_fwd): the value the samplers' generic element path
+ * forms.  The program's lp_const belongs to no observation and is left out.
+ *
+ * mc_program_num_elements returns M (host tables: also of a host-only
+ * program).  mc_program_enable_pointwise builds and uploads, once, a view of
+ * the terms and pools in the caller's order (the samplers' layouts are
+ * permuted: segment tiles, slice plans, index-sorted copies); programs that
+ * never call it pay nothing; MC_ERR_UNSUPPORTED, naming the term, for a term
+ * the pointwise kernel cannot evaluate.  Not a launch function (it allocates).
+ *
+ * mc_pointwise_stats: samples_dev is the samplers' [C, S, D] buffer (D the
+ * program's parameter count); stats_dev[f * M + o] (f64) receives, per
+ * observation o over the C * S draws, the fields below; matrix_dev is NULL or
+ * [C, S, M] f32 and then receives every pointwise value (small problems and
+ * tests).  A launch function: asynchronous, no allocation, no synchronisation;
+ * workspace_dev holds mc_pointwise_workspace_bytes(prog, C, S) bytes (0 is
+ * possible: workspace_dev may then be NULL).  The draws are split into blocks
+ * whose number depends on (C, S, the program) only and whose partials are
+ * merged in block order: two calls give the same bits, with or without
+ * matrix_dev.
+ *
+ * The six fields are a mergeable partial: two shards of draws combine exactly
+ * into the whole (max / rescale for the first two, Chan's update for mean and
+ * M2; with a non-finite draw on either side MEAN is the sum of the sides'
+ * non-finite MEANs and M2 is NaN).  Accumulation is f64.  Non-finite values
+ * follow NumPy float64 semantics: a -inf draw adds 0 to SUMEXP and makes MEAN
+ * -inf and M2 NaN; all draws -inf gives MAX = -inf and SUMEXP = 0 (no NaN in
+ * those two); a NaN draw makes MAX, SUMEXP and MEAN NaN.                     */
+#define MC_PW_MAX       0   /* max over draws of x                            */
+#define MC_PW_SUMEXP    1   /* sum over draws of exp(x - MAX)                 */
+#define MC_PW_N         2   /* draws counted                                  */
+#define MC_PW_MEAN      3   /* mean of x                                      */
+#define MC_PW_M2        4   /* sum of squared deviations from the mean        */
+#define MC_PW_NONFINITE 5   /* draws whose x is +-inf or NaN                  */
+#define MC_PW_COUNT     6
+int64_t mc_program_num_elements(const mc_program* prog);
+int mc_program_enable_pointwise(mc_program* prog);
+int64_t mc_pointwise_workspace_bytes(const mc_program* prog, int64_t C, int64_t S);
+int mc_pointwise_stats(const mc_program* prog, int64_t C, int64_t S,
+                       const float* samples_dev, double* stats_dev, float* matrix_dev,
+                       void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 const char* mc_last_error(void);
 int32_t mc_abi_version(void);
 

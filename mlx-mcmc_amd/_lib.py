@@ -52,6 +52,10 @@ MC_EXPR_MAX_NODES = 32
 MC_ST_ESS, MC_ST_MEAN, MC_ST_M2, MC_ST_HMEAN0, MC_ST_HMEAN1, MC_ST_HM2_0, MC_ST_HM2_1 = range(7)
 MC_ST_COUNT = 7
 
+# mc_pointwise_stats fields (include/mcmc355.h)
+MC_PW_MAX, MC_PW_SUMEXP, MC_PW_N, MC_PW_MEAN, MC_PW_M2, MC_PW_NONFINITE = range(6)
+MC_PW_COUNT = 6
+
 MC_OP_NONE = 0
 MC_OP_CONST = 1
 MC_OP_PSCALAR = 2
@@ -287,6 +291,11 @@ SIGNATURES = [
     ("mc_select", ctypes.c_int,
      [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _VP, ctypes.c_int64, ctypes.c_int64,
       ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), _VP, _VP, ctypes.c_int64, _VP]),
+    ("mc_program_num_elements", ctypes.c_int64, [_VP]),
+    ("mc_program_enable_pointwise", ctypes.c_int, [_VP]),
+    ("mc_pointwise_workspace_bytes", ctypes.c_int64, [_VP, ctypes.c_int64, ctypes.c_int64]),
+    ("mc_pointwise_stats", ctypes.c_int,
+     [_VP, ctypes.c_int64, ctypes.c_int64, _VP, _VP, _VP, _VP, ctypes.c_int64, _VP]),
     ("mc_last_error", ctypes.c_char_p, []),
     ("mc_abi_version", ctypes.c_int32, []),
 ]

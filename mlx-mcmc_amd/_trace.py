@@ -1041,16 +1041,22 @@ def stack(items) -> LogProbExpr:
 # ---------------------------------------------------------------------------
 # folding + program building
 # ---------------------------------------------------------------------------
-def fold_terms(terms: List[Term]) -> List[Term]:
+def fold_terms(terms: List[Term], adjacent_only: bool = False) -> List[Term]:
     """Merge terms that differ only in a constant/data `value`.
 
     ``for y in data: lp += Normal(mu, sigma).log_prob(y)`` yields one scalar
     term per observation; folding gives the single vector term the reference
     would have written as ``mx.sum(Normal(mu, sigma).log_prob(data))``.
+
+    ``adjacent_only``: a term joins only the term traced just before it, so the
+    elements keep their trace order (a pointwise likelihood's observation
+    order, ``trace(..., keep_order=True)``).
     """
     out: List[Term] = []
     groups: Dict[tuple, int] = {}
     for t in terms:
+        if adjacent_only:
+            groups = {k: v for k, v in groups.items() if v == len(out) - 1}
         foldable = (t.aff is None and t.value.kind in (_lib.MC_OP_CONST, _lib.MC_OP_DATA)
                     and t.loc.kind in (_lib.MC_OP_CONST, _lib.MC_OP_PSCALAR, _lib.MC_OP_NONE)
                     and t.scale.kind in (_lib.MC_OP_CONST, _lib.MC_OP_PSCALAR))
@@ -1142,7 +1148,7 @@ class TracedModel:
     n_nodes: int = 0
 
 
-def trace(log_prob_fn, initial_params: dict) -> TracedModel:
+def trace(log_prob_fn, initial_params: dict, keep_order: bool = False) -> TracedModel:
     layout = layout_of(initial_params)
     sym = {name: Param(name, off, shp)
            for name, shp, off in zip(layout.names, layout.shapes, layout.offsets)}
@@ -1156,7 +1162,7 @@ def trace(log_prob_fn, initial_params: dict) -> TracedModel:
     if out.shape != ():
         raise TraceError(f"log_prob must return a scalar (got shape {out.shape}); "
                          "sum the likelihood with mx.sum as the reference does")
-    terms = fold_terms(out.terms)
+    terms = fold_terms(out.terms, adjacent_only=keep_order)
     model = TracedModel(layout, terms, float(np.float32(out.const)))
     _build_pools(model)
     return model
@@ -1380,6 +1386,15 @@ class Program:
         2); 0 when the plan has no such term, or there is no plan."""
         return int(_lib.load().mc_program_lane_bundle(self.handle))
 
+    @property
+    def num_elements(self) -> int:
+        """mc_program_num_elements: the observations M of a likelihood program."""
+        return int(_lib.load().mc_program_num_elements(self.handle))
+
+    def enable_pointwise(self) -> None:
+        """Upload the caller-order view mc_pointwise_stats evaluates (once)."""
+        _lib.check(_lib.load().mc_program_enable_pointwise(self.handle))
+
     def __del__(self):
         h = getattr(self, "handle", None)
         if h is not None and h.value:
@@ -1518,4 +1533,15 @@ def compile_model(log_prob_fn, initial_params: dict, slices: int = 0,
         prog.set_slices(slices)
     if slice_kernel != "auto":
         prog.set_slice_kernel(slice_kernel)
+    return prog
+
+
+def pointwise_program(log_likelihood_fn, layout: ParamLayout) -> Program:
+    """A likelihood traced like ``log_prob`` over the parameters of ``layout``,
+    its terms in trace order (every element one observation), with the
+    pointwise view enabled (diagnostics.pointwise_log_likelihood)."""
+    _lib.require_device()
+    init = {n: np.zeros(shp, np.float32) for n, shp in zip(layout.names, layout.shapes)}
+    prog = Program(trace(log_likelihood_fn, init, keep_order=True))
+    prog.enable_pointwise()
     return prog

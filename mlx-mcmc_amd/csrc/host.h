@@ -165,7 +165,16 @@ struct mc_program {
     // the expression-term JIT's compiled kernels (jit.hip JitState), created
     // at the first launch that uses them
     mutable void* jit = nullptr;
+    // the pointwise view (run_pointwise.hip): the fused terms as validated,
+    // BEFORE an unsorted gather reorders them (expression terms: their rnodes),
+    // addressing the caller's pools — the first pw_n_data / pw_n_index entries of
+    // h_data / h_index — in the caller's element order; its device tables
+    // (PwView) exist only after mc_program_enable_pointwise
+    std::vector<DevTerm> pw_terms;
+    int64_t pw_n_data = 0, pw_n_index = 0;
+    void* pw = nullptr;
 };
+void pw_free(mc_program* p);  // (run_pointwise.hip)
 
 inline DevCtx ctx_of(const mc_program* p) {
     DevCtx c;

@@ -652,7 +652,7 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
 
     std::vector<float> dpool(data, data + n_data);
     std::vector<int32_t> ipool(index, index + n_index);
-    std::vector<DevTerm> dts, raws;
+    std::vector<DevTerm> dts, raws, pws;  // pws: the pointwise view (host.h pw_terms)
     std::vector<DevExprNode> gnodes, rnodes;
     int64_t max_n = 0;
     for (int32_t t = 0; t < n_terms; ++t) max_n = std::max<int64_t>(max_n, terms[t].n);
@@ -672,6 +672,7 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
                                            wpc);
             if (rc) return rc;
             raws.push_back(dt);
+            pws.push_back(dt);
             dts.push_back(dt);
             continue;
         }
@@ -789,6 +790,7 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
             }
         }
         dt.primary = primary;
+        DevTerm pwt = dt;  // the caller's element order and pools
         if (primary >= 0) {
             const int64_t ip = dt.op[primary].pool;
             bool sorted = true;
@@ -829,6 +831,9 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
              dt.op[2].kind == MC_OP_CONST))
             dt.clg = lgamma_norm(dt.dist, dt.op[1].cval, dt.op[2].cval);
         raws.push_back(dt);
+        pwt.clogs = dt.clogs;
+        pwt.clg = dt.clg;
+        pws.push_back(pwt);
         // pass planning: accumulating vector operands with overlapping parameter
         // ranges go to different sweeps
         int64_t lo[3], hi[3];
@@ -1024,6 +1029,9 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
     p->raw = raws;
     p->nodes = gnodes;
     p->rnodes = rnodes;
+    p->pw_terms = pws;
+    p->pw_n_data = n_data;
+    p->pw_n_index = n_index;
     p->ex = !gnodes.empty();
     p->h_data = dpool;
     p->h_index = ipool;
@@ -1132,6 +1140,7 @@ extern "C" int mc_debug_program_host_only(int on) {
 extern "C" int mc_program_destroy(mc_program* p) {
     if (!p) return MC_OK;
     jit_free(p);
+    pw_free(p);
     free_slices(p->sl);
     free_lanes(p->lr);
     if (p->d_terms) (void)hipFree(p->d_terms);

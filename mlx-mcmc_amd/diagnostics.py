@@ -17,7 +17,18 @@ values) or a handful of order statistics come back to the host.
   mean / std from per-series moments, median and percentiles from exact
   device order statistics, interpolated with numpy's own rule.
 
-No CPU fallback: without the library these raise ``EngineUnavailable``.
+* ``pointwise_log_likelihood(log_likelihood, samples, layout)`` — for every
+  observation of a likelihood traced like ``log_prob``, six mergeable
+  statistics of its log-likelihood over the kept draws (mc_pointwise_stats,
+  csrc/pointwise.h): the C x S x M matrix is never stored.  ``waic`` forms
+  WAIC from them (Vehtari, Gelman and Gabry 2017); ``merge_pointwise`` is the
+  host statement of the merge the device and the ranks apply.  Out of scope:
+  PSIS-LOO (a per-observation tail fit over draws; ``matrix=True`` hands small
+  problems to other tools), posterior predictive sampling, and the expression
+  JIT for likelihoods (expression terms run the node interpreter).
+
+No CPU fallback: without the library these raise ``EngineUnavailable``
+(``merge_pointwise`` and ``waic_from_stats`` are pure host arithmetic).
 """
 from __future__ import annotations
 
@@ -247,3 +258,176 @@ def summarize(samples, layout=None, credible_interval: float = 0.95) -> Dict[str
             f'{upper_pct:.1f}%': float(hi),
         }
     return out
+
+
+# ------------------------------------------------- pointwise / WAIC -----
+PW_FIELDS = ("max", "sumexp", "n", "mean", "m2", "nonfinite")
+
+
+def merge_pointwise(parts):
+    """Merge pointwise partials (dicts of the six [M] float64 arrays of
+    ``pointwise_log_likelihood``, each over its own shard of draws) in order.
+
+    max / rescale for ``max`` and ``sumexp``, Chan's update for ``mean`` and
+    ``m2``; where a side holds a non-finite draw, ``mean`` is the sum of the
+    sides' non-finite means (-inf, +inf or NaN, as np.mean of the whole gives)
+    and ``m2`` is NaN (as np.var gives).  The device merge (csrc/pointwise.h
+    pw_merge) and the rank merge apply the same rules."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_pointwise needs at least one partial")
+    acc = {f: np.array(parts[0][f], dtype=np.float64, copy=True) for f in PW_FIELDS}
+    with np.errstate(all="ignore"):
+        for p in parts[1:]:
+            b = {f: np.asarray(p[f], np.float64) for f in PW_FIELDS}
+            am, bm = acc["max"], b["max"]
+            m = np.where((bm > am) | np.isnan(bm), bm, am)
+            sa = np.where(am == m, acc["sumexp"], acc["sumexp"] * np.exp(am - m))
+            sb = np.where(bm == m, b["sumexp"], b["sumexp"] * np.exp(bm - m))
+            na, nb = acc["n"], b["n"]
+            n = na + nb
+            anf, bnf = acc["nonfinite"] > 0, b["nonfinite"] > 0
+            d = b["mean"] - acc["mean"]
+            r = 1.0 / n
+            mean = acc["mean"] + d * (nb * r)
+            m2 = acc["m2"] + (b["m2"] + d * d * (na * nb * r))
+            cls = np.where(anf, np.where(bnf, acc["mean"] + b["mean"], acc["mean"]), b["mean"])
+            nf = anf | bnf
+            acc = {"max": m, "sumexp": sa + sb, "n": n,
+                   "mean": np.where(nf, cls, mean), "m2": np.where(nf, np.nan, m2),
+                   "nonfinite": acc["nonfinite"] + b["nonfinite"]}
+    return acc
+
+
+def _gather_parts(part, group):
+    """Every rank's partial, in rank order (one rank: the partial itself)."""
+    import torch.distributed as dist
+
+    if group is False or not (dist.is_available() and dist.is_initialized()) \
+            or dist.get_world_size(group) <= 1:
+        return [part]
+    out = [None] * dist.get_world_size(group)
+    dist.all_gather_object(out, part, group=group)
+    return out
+
+
+def _pointwise_inputs(samples, layout):
+    """([C, S, D] device tensor, layout) from a device buffer with its layout,
+    or from a dict name -> array as ``MCMC.samples`` holds it: [C, S, *shape],
+    or [S, *shape] for one chain.  Without a layout the parameter shapes are
+    what follows the leading axes: one chain when some array is 1-D, else
+    [C, S, ...] (pass the run's layout for one chain of vector parameters)."""
+    from . import _trace
+
+    if not isinstance(samples, dict):
+        if layout is None:
+            raise ValueError("a [C, S, D] buffer needs its layout")
+        x = _as_device(samples)
+        if x.shape[2] != layout.size:
+            raise ValueError(f"samples have {x.shape[2]} elements per draw, the layout "
+                             f"{layout.size}")
+        return x, layout
+    arrs = {k: np.asarray(_trace._to_numpy(v), np.float32) for k, v in samples.items()}
+    if not arrs:
+        raise ValueError("samples is empty")
+    if layout is not None:
+        lead = {a.ndim - len(shp) for a, shp in
+                ((arrs[n], s) for n, s in zip(layout.names, layout.shapes))}
+        if len(lead) != 1 or lead not in ({1}, {2}):
+            raise ValueError("samples do not match the layout's parameter shapes")
+        lead = lead.pop()
+        names = layout.names
+    else:
+        lead = 1 if min(a.ndim for a in arrs.values()) == 1 else 2
+        names = list(arrs)
+    first = arrs[names[0]]
+    C, S = (1, first.shape[0]) if lead == 1 else first.shape[:2]
+    cols = []
+    for n in names:
+        a = arrs[n]
+        if a.shape[:lead] != first.shape[:lead]:
+            raise ValueError(f"parameter '{n}' has leading shape {a.shape[:lead]}, expected "
+                             f"{first.shape[:lead]}")
+        cols.append(a.reshape(C, S, -1))
+    lay = _trace.layout_of({n: np.zeros(arrs[n].shape[lead:], np.float32) for n in names})
+    if layout is not None and list(lay.shapes) != [tuple(s) for s in layout.shapes]:
+        raise ValueError("samples do not match the layout's parameter shapes")
+    return _as_device(np.concatenate(cols, axis=2)), lay
+
+
+def pointwise_log_likelihood(log_likelihood_fn, samples, layout=None, *, matrix=False,
+                             group=None):
+    """Per-observation log-likelihood statistics over the kept draws.
+
+    ``log_likelihood_fn(params)`` is written and traced exactly like
+    ``log_prob`` and returns a scalar, normally
+    ``mx.sum(Dist(...).log_prob(y))``.  Every element of every term of that
+    trace is one observation, term by term in trace order and inside a term in
+    the user's element order (M in all); the value of element i of term t is
+    ``weight_t * lp_{t,i}`` as one f32 product (``mx.mean`` scales every
+    observation by 1 / n).  Constants added to the likelihood belong to no
+    observation and are left out; nothing guesses which terms of a ``log_prob``
+    are observed — pass the likelihood alone.
+
+    ``samples``: a [C, S, D] device tensor with its ``layout``, or a dict name
+    -> array as ``MCMC.samples`` holds it.  Returns the six statistics
+    (``max``, ``sumexp`` = sum exp(x - max), ``n``, ``mean``, ``m2``,
+    ``nonfinite``) as float64 NumPy [M] arrays — a partial ``merge_pointwise``
+    can combine with other shards of draws — plus ``matrix``, the [C, S, M]
+    float32 device tensor of every value, when ``matrix=True`` (small problems
+    only).  With an initialised process group (``group=False`` stays local)
+    the ranks' partials are gathered and merged in rank order; the matrix
+    stays this rank's."""
+    import torch
+
+    from . import _trace
+
+    x, lay = _pointwise_inputs(samples, layout)
+    C, S, D = x.shape
+    prog = _trace.pointwise_program(log_likelihood_fn, lay)
+    lib = _lib.load()
+    M = prog.num_elements
+    st = torch.empty((_lib.MC_PW_COUNT, M), dtype=torch.float64, device=x.device)
+    mat = torch.empty((C, S, M), dtype=torch.float32, device=x.device) if matrix else None
+    nb = lib.mc_pointwise_workspace_bytes(prog.handle, C, S)
+    if nb < 0:
+        _lib.check(int(nb))
+    ws = torch.empty(max(int(nb), 1), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.mc_pointwise_stats(prog.handle, C, S, _lib.ptr(x), _lib.ptr(st),
+                                      _lib.ptr(mat), _lib.ptr(ws), nb, _lib.stream_handle()))
+    host = st.cpu().numpy()   # (synchronises: prog, x and ws outlive the launch)
+    part = {f: host[k].copy() for k, f in enumerate(PW_FIELDS)}
+    out = merge_pointwise(_gather_parts(part, group))
+    if matrix:
+        out["matrix"] = mat
+    return out
+
+
+def waic_from_stats(stats) -> dict:
+    """WAIC (Vehtari, Gelman and Gabry 2017) from the pointwise statistics:
+    lppd_i = log(sumexp) + max - log n, p_waic_i = m2 / (n - 1) (the sample
+    variance, NaN for one draw), elpd_i = lppd_i - p_waic_i."""
+    with np.errstate(all="ignore"):
+        n = np.asarray(stats["n"], np.float64)
+        lppd_i = np.log(stats["sumexp"]) + stats["max"] - np.log(n)
+        p_i = np.asarray(stats["m2"], np.float64) / (n - 1.0)
+        elpd_i = lppd_i - p_i
+        m = elpd_i.size
+        elpd = float(np.sum(elpd_i))
+        return {"elpd_waic": elpd, "p_waic": float(np.sum(p_i)), "waic": -2.0 * elpd,
+                "se": float(np.sqrt(m * np.var(elpd_i))), "lppd": float(np.sum(lppd_i)),
+                "pointwise": {"lppd": lppd_i, "p_waic": p_i, "elpd_waic": elpd_i},
+                "n_obs": int(m), "n_draws": int(n.max()) if m else 0,
+                "n_high_p_waic": int(np.sum(p_i > 0.4)),
+                "n_nonfinite": int(np.sum(stats["nonfinite"]))}
+
+
+def waic(log_likelihood_fn, samples, layout=None, *, group=None) -> dict:
+    """WAIC of a likelihood over the kept draws (``pointwise_log_likelihood``'s
+    arguments): ``elpd_waic``, ``p_waic``, ``waic`` (= -2 elpd), ``se``
+    (= sqrt(M var_i elpd_i)), ``lppd``, the ``pointwise`` terms, ``n_obs``,
+    ``n_draws``, ``n_high_p_waic`` (observations with p_waic_i > 0.4, where
+    WAIC is unreliable) and ``n_nonfinite`` (draws outside an observation's
+    support: reported, never raised)."""
+    return waic_from_stats(pointwise_log_likelihood(log_likelihood_fn, samples, layout,
+                                                    group=group))

@@ -135,6 +135,27 @@ class MCMC:
                          "r_hat": d["rhat"][off:off + n].reshape(shape)}
         return out
 
+    def _kept_draws(self):
+        if self.samples is None:
+            raise ValueError("Must run sampling first. Call run() method.")
+        dev = getattr(self.info, "device_samples", None)
+        if dev is not None:
+            return dev, self.info.layout
+        return self.samples, getattr(self.info, "layout", None)
+
+    def pointwise_log_likelihood(self, log_likelihood_fn, matrix=False):
+        """Per-observation log-likelihood statistics of ``log_likelihood_fn``
+        (traced like ``log_prob``) over the kept draws, on the device
+        (diagnostics.pointwise_log_likelihood)."""
+        samples, layout = self._kept_draws()
+        return _diag.pointwise_log_likelihood(log_likelihood_fn, samples, layout,
+                                              matrix=matrix, group=False)
+
+    def waic(self, log_likelihood_fn):
+        """WAIC of ``log_likelihood_fn`` over the kept draws (diagnostics.waic)."""
+        samples, layout = self._kept_draws()
+        return _diag.waic(log_likelihood_fn, samples, layout, group=False)
+
     def print_summary(self, credible_interval=0.95):
         summary = self.summary(credible_interval)
         print("\nPosterior Summary:")
