@@ -2,8 +2,9 @@
 // libmcmc355.so (program.hip: program builder, slicing policy and queries;
 // plan_slices.hip, plan_lanes.hip: the planners, declared in plan.h; api.hip:
 // tape / state / metric / diagnostics launches and the rest of the C-ABI;
-// run_hmc.hip, run_mh.hip, run_nuts.hip: the sampler launches).  Helpers are `inline` so that every unit shares one
-// definition (and one copy of the caches and workspace tag tables).
+// run_hmc.hip, run_mh.hip, run_nuts.hip and the run_lanes_rs* / run_*_sl units:
+// the sampler launches, on launch.h).  Helpers are `inline` so that every unit
+// shares one definition (and one copy of the caches and workspace tag tables).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -71,6 +72,12 @@ inline float dist_c0(int dist) {
     if (dist == MC_DIST_NORMAL) return c_log_norm();
     if (dist == MC_DIST_HALFNORMAL) return c_log2() + c_log_norm();
     return 0.0f;
+}
+
+// An environment switch that is on unless the variable starts with '0'.
+inline bool env_on(const char* name) {
+    const char* e = std::getenv(name);
+    return !(e && e[0] == '0');
 }
 
 // ---------------------------------------------------------------------------
@@ -328,8 +335,8 @@ static constexpr int64_t kLrAutoMinElements = 2048;
 // Why the program's expression terms do not take the lane layout ("" when
 // they do, or when it has none).
 inline std::string expr_lanes_why(const mc_program* p) {
-    if (const char* e = std::getenv("MC_EXPR_LANES"))  // 0: the tape (A/B, tests)
-        if (e[0] == '0') return "expression terms on the lanes are switched off (MC_EXPR_LANES=0)";
+    if (!env_on("MC_EXPR_LANES"))  // 0: the tape (A/B, tests)
+        return "expression terms on the lanes are switched off (MC_EXPR_LANES=0)";
     char buf[256];
     bool grouped = false;
     for (const DevTerm& t : p->raw) {
@@ -470,6 +477,30 @@ inline int dispatch_tape(const mc_program* p, bool lds, F&& f) {
         default: return arena(std::integral_constant<int, 8>{});
     }
 }
+// The instantiation of a lane-layout launcher (lanes.h) for a program:
+// register slots per lane RS (1, 2 or 4) and shared-parameter slots NSH (3, or
+// 4 with more than 3 shared parameters).  A site whose kernels fix one of the
+// two (a translation unit per RS, a compile-time form's NSH) takes the other
+// ladder alone, so that no unit instantiates a kernel it does not launch.
+template <typename F>
+inline int dispatch_rs(const mc_program* p, F&& f) {
+    switch (p->lr.rs) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
+}
+template <typename F>
+inline int dispatch_nsh(const mc_program* p, F&& f) {
+    return p->lr.Dsh > 3 ? f(std::integral_constant<int, 4>{})
+                         : f(std::integral_constant<int, 3>{});
+}
+template <typename F>
+inline int dispatch_lanes(const mc_program* p, F&& f) {
+    return dispatch_rs(p, [&](auto RS) {
+        return dispatch_nsh(p, [&](auto NSH) { return f(RS, NSH); });
+    });
+}
 // ---------------------------------------------------------------------------
 // diagonal metric (metric.h): buffer layout and the MET kernels' argument
 // ---------------------------------------------------------------------------
@@ -601,6 +632,11 @@ inline int64_t sl_groups_per_launch(const mc_program* p, int64_t C) {
     return std::min(groups, cap);
 }
 static constexpr int64_t kSlStatusBytes = 256;
+// dynamic LDS bytes of the lane layout itself: the slice block and the scalar
+// terms (k_nuts_lr and k_nuts_sl add their arenas after it)
+inline size_t lr_base_lds_bytes(const mc_program* p) {
+    return (size_t)p->lr.sdata_floats * 4 + p->lr.sterms.size() * sizeof(LrSterm);
+}
 // waves per workgroup of the lane-resident kernel: 8 (16 chains, two waves per
 // SIMD) for up to 16 slices... 4 (8 chains, one wave per SIMD) for <= 8 slices
 // one slice: one wave per workgroup (no exchange, so no block structure to
@@ -680,10 +716,7 @@ inline bool ws_reserve(const void* ws, uint64_t need, uint64_t bytes, uint32_t* 
 // MC_LANES_FAST=0 in the environment (A/B timing against k_hmc_lr)
 inline int g_lanes_fast = -1;  // mc_debug_lanes_fast; -1: MC_LANES_FAST from the environment
 inline bool lanes_fast_enabled() {
-    if (g_lanes_fast < 0) {
-        const char* e = std::getenv("MC_LANES_FAST");
-        g_lanes_fast = (e && e[0] == '0') ? 0 : 1;
-    }
+    if (g_lanes_fast < 0) g_lanes_fast = env_on("MC_LANES_FAST");
     return g_lanes_fast == 1;
 }
 
@@ -691,10 +724,7 @@ inline bool lanes_fast_enabled() {
 // mc_debug_lanes_forms(0) selects the run-time form kernel (A/B timing, tests)
 inline int g_lanes_forms = -1;
 inline bool lanes_forms_enabled() {
-    if (g_lanes_forms < 0) {
-        const char* e = std::getenv("MC_LANES_FORM");
-        g_lanes_forms = (e && e[0] == '0') ? 0 : 1;
-    }
+    if (g_lanes_forms < 0) g_lanes_forms = env_on("MC_LANES_FORM");
     return g_lanes_forms == 1;
 }
 

@@ -1,6 +1,5 @@
 // run_hmc.hip — HMC launches (k_hmc_lf, k_hmc_lr, k_hmc_sl, k_hmc) and mc_hmc_run.
-#include "host.h"
-#include "jit.h"
+#include "launch.h"
 
 extern "C" int mc_workspace_release(const void* ws) {
     if (ws) ws_forget(ws);
@@ -31,10 +30,7 @@ static __global__ void k_xcc_probe(uint32_t* out) {
     if (threadIdx.x == 0) out[blockIdx.x] = x;
 }
 bool xcd_round_robin(int64_t grid, int S) {
-    if (g_xcd_local < 0) {
-        const char* e = std::getenv("MC_XCD_LOCAL");
-        g_xcd_local = (e && e[0] == '0') ? 0 : 1;
-    }
+    if (g_xcd_local < 0) g_xcd_local = env_on("MC_XCD_LOCAL");
     if (g_xcd_local == 0 || S < 2 || grid % 8 != 0 || (grid / 8) % S != 0) return false;
     static std::mutex mu;
     static std::map<std::pair<int, int64_t>, bool> cache;
@@ -82,43 +78,31 @@ static int launch_hmc_sl(const mc_program* p, const mc_run_config* cfg, void* st
     if (!interp_ok(p))
         return fail(MC_ERR_UNSUPPORTED, "the term interpreter does not run transformed operands "
                     "or affine locs");
-    int64_t qo, go;
-    mc_state_offsets(p, cfg->num_chains, &qo, &go);
-    char* b = (char*)state;
-    RunArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.cfg = *cfg;
+    RunState R = run_state(p, cfg, state);
     const SlCtx ctx = slctx_of(p);
-    const size_t lds = (size_t)SlLayout<NB>(ctx).total * 4;
-    MC_HIP_TRY(allow_lds(k_hmc_sl<NB>, lds));
-    const int64_t C = cfg->num_chains;
-    const int64_t groups = (C + NB - 1) / NB;
-    const int64_t gpl = sl_groups_per_launch(p, C);
-    const int64_t used = sl_workspace_bytes(p, C);
+    const TraceDev td = trace_of(tr);
+    ExchangeLaunch d;
+    d.name = "sliced HMC";
+    d.threads = kSlLanes * NB / 2;
+    d.chains = NB;
+    d.S = p->sl.S;
+    d.lds = (size_t)SlLayout<NB>(ctx).total * 4;
+    d.blocks_per_launch = sl_groups_per_launch(p, cfg->num_chains);
+    d.clear_bytes = sl_workspace_bytes(p, cfg->num_chains);
+    d.tags_per_launch = 0;
+    // the kernel takes no tag base: its tags restart at 1 in every launch, so
+    // the granules (and, first, the status word) are cleared ahead of each, and
+    // the lane-resident kernel must clear again after it
+    d.restart_tags = true;
+    d.coresident = true;
     int* status = (int*)ws;
     unsigned long long* xch = (unsigned long long*)((char*)ws + kSlStatusBytes);
-    const int64_t cap = resident_capacity(k_hmc_sl<NB>, kSlLanes * NB / 2, lds);
-    if (cap < std::min(gpl, groups) * p->sl.S)
-        return fail(MC_ERR_UNSUPPORTED,
-                    "sliced HMC: %lld workgroups must be co-resident, the device holds %lld of "
-                    "this kernel", (long long)(std::min(gpl, groups) * p->sl.S), (long long)cap);
-    A.fault = g_exchange_fault;
-    ws_forget(ws);  // its tags restart at 1: the lane-resident kernel must clear again
-    ws_mark_status(ws);
-    for (int64_t g0 = 0; g0 < groups; g0 += gpl) {
-        const int64_t ng = std::min(gpl, groups - g0);
-        // the exchange tags restart at 1 in every launch: clear the granules
-        // (and, first, the status word) ahead of it
-        MC_HIP_TRY(hipMemsetAsync(g0 == 0 ? ws : (void*)xch, 0,
-                                  g0 == 0 ? used : used - kSlStatusBytes, st));
-        const int64_t grid = ng * p->sl.S;
-        const hipError_t e = launch_exchange(k_hmc_sl<NB>, grid, kSlLanes * NB / 2, lds, st, ctx,
-                                             A, g0 * NB, ng, (mc_chain_scalars*)b,
-                                             (float*)(b + qo), (float*)(b + go), samples,
-                                             trace_of(tr), xch, status);
-        MC_HIP_TRY(e);
-    }
-    return MC_OK;
+    auto k = static_pair(k_hmc_sl<NB>, k_hmc_sl<NB>);  // (no L2-resident variant)
+    return run_exchange(d, k, cfg->num_chains, ws, st, R.A,
+                        [&](int64_t g0, int64_t ng, int64_t grid, bool xl, uint32_t) {
+        return k.launch(xl, grid, d.threads, d.lds, st, ctx, R.A, g0 * NB, ng, R.scalars, R.q, R.g,
+                        samples, td, xch, status);
+    });
 }
 
 extern "C" int mc_workspace_status(const mc_program* p, const void* ws, int64_t bytes,
@@ -161,126 +145,111 @@ extern "C" int64_t mc_hmc_workspace_bytes(const mc_program* p, int64_t C) {
 // MET: the metric instantiation (metric.h) on the buffer `metric`; minv and
 // msqrt join the arena in LDS when the two extra vectors still fit its budget
 // (the arena decision itself, and so the workspace, is the one without a metric)
-template <int WPC, bool LDS, bool EX, bool MET = false>
+template <int WPC, bool LDS, bool EX, bool MET>
 static int launch_hmc(const mc_program* p, const mc_run_config* cfg, void* state,
-                      float* samples, const mc_trace* tr, float* ws, hipStream_t st,
-                      void* metric = nullptr, int adapt = 0) {
-    int64_t qo, go;
-    mc_state_offsets(p, cfg->num_chains, &qo, &go);
-    char* b = (char*)state;
-    RunArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.cfg = *cfg;
+                      float* samples, const mc_trace* tr, float* ws, hipStream_t st, void* metric,
+                      int adapt) {
+    RunState R = run_state(p, cfg, state);
+    RunArgs& A = R.A;
     A.dpad = dpad_of(p->D);
     A.lds_floats = (int32_t)hmc_lds_floats(p, LDS);
     A.scratch_floats = scratch_of(p);
-    MetricDev M = {};
+    bool ml = false;
     if constexpr (MET) {
-        const bool ml = LDS && cpb_of(WPC) * (A.lds_floats + 2 * (int64_t)A.dpad) * 4 <= kLdsArenaBudget;
+        ml = LDS && cpb_of(WPC) * (A.lds_floats + 2 * (int64_t)A.dpad) * 4 <= kLdsArenaBudget;
         if (ml) A.lds_floats += 2 * A.dpad;
-        M = metricdev_of(p, cfg->num_chains, metric, adapt, ml);
     }
     const size_t lds = (size_t)cpb_of(WPC) * A.lds_floats * 4;
     const int64_t grid = (cfg->num_chains + cpb_of(WPC) - 1) / cpb_of(WPC);
-    if constexpr (EX) {  // the program's expression terms compiled (jit.hip)
-        DevCtx ctx = ctx_of(p);
-        mc_chain_scalars* scal = (mc_chain_scalars*)b;
-        float *sq = (float*)(b + qo), *sg = (float*)(b + go);
-        TraceDev td = trace_of(tr);
-        void* args[] = {&ctx, &A, &scal, &sq, &sg, &samples, &td, &ws, &M};  // (M: MET only)
-        bool used = false;
-        const int rc = jit_launch(p, "mc::k_hmc<" + std::to_string(WPC) + ", " +
-                                         (LDS ? "true" : "false") +
-                                         (MET ? ", true, true, mc::MetricDev>" : ", true>"),
-                                  (unsigned)grid, block_of(WPC), lds, st, args, &used);
-        if (rc != MC_OK || used) return rc;
-    }
-    if constexpr (MET) {
-        auto kern = k_hmc<WPC, LDS, EX, true, MetricDev>;
-        MC_HIP_TRY(allow_lds(kern, lds));
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block_of(WPC)), lds, st, ctx_of(p), A,
-                           (mc_chain_scalars*)b, (float*)(b + qo), (float*)(b + go), samples,
-                           trace_of(tr), ws, M);
-    } else {
-        MC_HIP_TRY(allow_lds(k_hmc<WPC, LDS, EX>, lds));
-        hipLaunchKernelGGL((k_hmc<WPC, LDS, EX>), dim3((unsigned)grid), dim3(block_of(WPC)), lds,
-                           st, ctx_of(p), A, (mc_chain_scalars*)b, (float*)(b + qo),
-                           (float*)(b + go), samples, trace_of(tr), ws);
-    }
-    MC_HIP_TRY(hipGetLastError());
+    // (EX: the program's expression terms compiled, jit.hip)
+    const std::string jit = !EX ? "" : "mc::k_hmc<" + std::to_string(WPC) + ", " +
+                                           (LDS ? "true" : "false") +
+                                           (MET ? ", true, true, mc::MetricDev>" : ", true>");
+    auto go = [&](auto kern, auto... met) {
+        return launch_tape(p, kern, jit, grid, block_of(WPC), lds, st, ctx_of(p), A, R.scalars,
+                           R.q, R.g, samples, trace_of(tr), ws, met...);
+    };
+    if constexpr (MET)
+        return go(k_hmc<WPC, LDS, EX, true, MetricDev>,
+                  metricdev_of(p, cfg->num_chains, metric, adapt, ml));
+    else
+        return go(k_hmc<WPC, LDS, EX>);
+}
+
+// A run that takes an exchange kernel (sliced or lane-resident).  L = 0 with
+// transformed operands: the interpreter (k_hmc_sl) declines them, so such a
+// run takes the chain-per-workgroup tape (as lanes1 does)
+static bool hmc_exchange_route(const mc_program* p, const mc_run_config* cfg) {
+    const bool sl_tape = sliced(p) && !use_lanes(p, cfg) && !interp_ok(p);
+    return (sliced(p) && !sl_tape) || (lanes1(p) && use_lanes(p, cfg));
+}
+
+// What mc_hmc_run and mc_hmc_run_metric check first (met: the metric entry)
+static int hmc_validate(const mc_program* p, const mc_run_config* cfg, void* state, bool met,
+                        const void* metric) {
+    int rc = check_cfg(p, cfg, state);
+    if (rc) return rc;
+    if (met && !metric) return fail(MC_ERR_INVALID, "metric buffer is NULL");
+    if (cfg->num_leapfrog_steps < 0) return fail(MC_ERR_INVALID, "num_leapfrog_steps < 0");
     return MC_OK;
+}
+
+// ... and where both end: k_hmc on the tape (metric: the MET instantiation)
+template <bool MET>
+static int hmc_tape(const mc_program* p, const mc_run_config* cfg, void* state, float* samples,
+                    const mc_trace* tr, void* ws, int64_t ws_bytes, void* stream, void* metric,
+                    int adapt) {
+    ws_forget(ws);
+    const bool lds = hmc_use_lds(p);
+    const int64_t need = mc_hmc_workspace_bytes(p, cfg->num_chains);
+    if (!lds && (ws == nullptr || ws_bytes < need))
+        return fail(MC_ERR_INVALID, "workspace too small: need %lld bytes", (long long)need);
+    return dispatch_tape(p, lds, [&](auto W, auto L, auto E) {
+        return launch_hmc<decltype(W)::value, decltype(L)::value, decltype(E)::value, MET>(
+            p, cfg, state, samples, tr, (float*)ws, (hipStream_t)stream, metric, adapt);
+    });
 }
 
 extern "C" int mc_hmc_run(const mc_program* p, const mc_run_config* cfg, void* state,
                           float* samples, const mc_trace* tr, void* ws, int64_t ws_bytes,
                           void* stream) {
-    int rc = check_cfg(p, cfg, state);
+    int rc = hmc_validate(p, cfg, state, false, nullptr);
     if (rc) return rc;
-    if (cfg->num_leapfrog_steps < 0) return fail(MC_ERR_INVALID, "num_leapfrog_steps < 0");
     if (cfg->num_chains == 0 || cfg->iter_count == 0) return MC_OK;
-    // L = 0 with transformed operands: the interpreter (k_hmc_sl) declines
-    // them, so such a run takes the chain-per-workgroup tape (as lanes1 does)
-    const bool sl_tape = sliced(p) && !use_lanes(p, cfg) && !interp_ok(p);
-    if ((sliced(p) && !sl_tape) || (lanes1(p) && use_lanes(p, cfg))) {
+    if (hmc_exchange_route(p, cfg)) {
         const int64_t need = sl_workspace_bytes(p, cfg->num_chains);
         if (ws == nullptr || ws_bytes < need)
             return fail(MC_ERR_INVALID, "workspace too small: need %lld bytes", (long long)need);
         if (device_cus() <= 0) return fail(MC_ERR_HIP, "no HIP device");
-        int rc = kLanesNoJit;
-        if (use_lanes(p, cfg)) {
-            hipStream_t st = (hipStream_t)stream;
-            switch (p->lr.rs) {  // (one translation unit per slot count: run_lanes_rs*.hip)
-                case 1: rc = hmc_lanes_rs1(p, cfg, state, samples, tr, ws, st); break;
-                case 2: rc = hmc_lanes_rs2(p, cfg, state, samples, tr, ws, st); break;
-                default: rc = hmc_lanes_rs4(p, cfg, state, samples, tr, ws, st); break;
-            }
-            // an expression program without its JIT-compiled lane kernel (the
-            // JIT off or failed): the tape below
-            if (rc != kLanesNoJit) return rc;
-        } else {
+        hipStream_t st = (hipStream_t)stream;
+        if (!use_lanes(p, cfg))
             return sl_nb_for(p, cfg->num_chains) == 16
-                       ? launch_hmc_sl<16>(p, cfg, state, samples, tr, ws, (hipStream_t)stream)
-                       : launch_hmc_sl<8>(p, cfg, state, samples, tr, ws, (hipStream_t)stream);
+                       ? launch_hmc_sl<16>(p, cfg, state, samples, tr, ws, st)
+                       : launch_hmc_sl<8>(p, cfg, state, samples, tr, ws, st);
+        switch (p->lr.rs) {  // (one translation unit per slot count: run_lanes_rs*.hip)
+            case 1: rc = hmc_lanes_rs1(p, cfg, state, samples, tr, ws, st); break;
+            case 2: rc = hmc_lanes_rs2(p, cfg, state, samples, tr, ws, st); break;
+            default: rc = hmc_lanes_rs4(p, cfg, state, samples, tr, ws, st); break;
         }
+        // an expression program without its JIT-compiled lane kernel (the
+        // JIT off or failed): the tape below
+        if (rc != kLanesNoJit) return rc;
     }
-    ws_forget(ws);
-    const bool lds = hmc_use_lds(p);
-    const int64_t need = mc_hmc_workspace_bytes(p, cfg->num_chains);
-    if (!lds && (ws == nullptr || ws_bytes < need))
-        return fail(MC_ERR_INVALID, "workspace too small: need %lld bytes", (long long)need);
-    hipStream_t st = (hipStream_t)stream;
-    float* w = (float*)ws;
-    return dispatch_tape(p, lds, [&](auto W, auto L, auto E) {
-        return launch_hmc<decltype(W)::value, decltype(L)::value, decltype(E)::value>(
-            p, cfg, state, samples, tr, w, st);
-    });
+    return hmc_tape<false>(p, cfg, state, samples, tr, ws, ws_bytes, stream, nullptr, 0);
 }
 
 extern "C" int mc_hmc_run_metric(const mc_program* p, const mc_run_config* cfg, void* state,
                                  float* samples, const mc_trace* tr, void* ws, int64_t ws_bytes,
                                  void* metric, int32_t adapt, void* stream) {
-    int rc = check_cfg(p, cfg, state);
+    int rc = hmc_validate(p, cfg, state, true, metric);
     if (rc) return rc;
-    if (!metric) return fail(MC_ERR_INVALID, "metric buffer is NULL");
-    if (cfg->num_leapfrog_steps < 0) return fail(MC_ERR_INVALID, "num_leapfrog_steps < 0");
-    const bool sl_tape = sliced(p) && !use_lanes(p, cfg) && !interp_ok(p);
-    if ((sliced(p) && !sl_tape) || (lanes1(p) && use_lanes(p, cfg)))
+    if (hmc_exchange_route(p, cfg))
         return fail(MC_ERR_UNSUPPORTED,
                     "a metric runs on the chain-per-workgroup kernel k_hmc only and this program "
                     "is planned onto a sliced or lane-resident kernel: "
                     "mc_program_set_slices(prog, 1) keeps it on k_hmc");
     if (cfg->num_chains == 0 || cfg->iter_count == 0) return MC_OK;
-    ws_forget(ws);
-    const bool lds = hmc_use_lds(p);
-    const int64_t need = mc_hmc_workspace_bytes(p, cfg->num_chains);
-    if (!lds && (ws == nullptr || ws_bytes < need))
-        return fail(MC_ERR_INVALID, "workspace too small: need %lld bytes", (long long)need);
-    hipStream_t st = (hipStream_t)stream;
-    float* w = (float*)ws;
-    return dispatch_tape(p, lds, [&](auto W, auto L, auto E) {
-        return launch_hmc<decltype(W)::value, decltype(L)::value, decltype(E)::value, true>(
-            p, cfg, state, samples, tr, w, st, metric, adapt);
-    });
+    return hmc_tape<true>(p, cfg, state, samples, tr, ws, ws_bytes, stream, metric, adapt);
 }
 
 #ifdef MC_STAMPS

@@ -1,6 +1,4 @@
 // run_mh.hip — Metropolis-Hastings launches (k_mh) and mc_mh_run.
-#include "host.h"
-#include "jit.h"
 #include "run_mh_sl.h"
 
 // ---- Metropolis-Hastings (metropolis.py:6-101) --------------------------------
@@ -32,35 +30,17 @@ extern "C" int64_t mc_mh_workspace_bytes(const mc_program* p, int64_t C) {
 template <int WPC, bool LDS, bool EX>
 static int launch_mh(const mc_program* p, const mc_run_config* cfg, float scale, void* state,
                      float* samples, const mc_trace* tr, float* ws, hipStream_t st) {
-    int64_t qo, go;
-    mc_state_offsets(p, cfg->num_chains, &qo, &go);
-    char* b = (char*)state;
-    RunArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.cfg = *cfg;
-    A.dpad = dpad_of(p->D);
-    A.lds_floats = (int32_t)mh_lds_floats(p, LDS);
-    A.scratch_floats = scratch_of(p);
-    const size_t lds = (size_t)cpb_of(WPC) * A.lds_floats * 4;
+    RunState R = run_state(p, cfg, state);
+    R.A.dpad = dpad_of(p->D);
+    R.A.lds_floats = (int32_t)mh_lds_floats(p, LDS);
+    R.A.scratch_floats = scratch_of(p);
+    const size_t lds = (size_t)cpb_of(WPC) * R.A.lds_floats * 4;
     const int64_t grid = (cfg->num_chains + cpb_of(WPC) - 1) / cpb_of(WPC);
-    if constexpr (EX) {  // the program's expression terms compiled (jit.hip)
-        DevCtx ctx = ctx_of(p);
-        mc_chain_scalars* scal = (mc_chain_scalars*)b;
-        float* sq = (float*)(b + qo);
-        TraceDev td = trace_of(tr);
-        void* args[] = {&ctx, &A, &scale, &scal, &sq, &samples, &td, &ws};
-        bool used = false;
-        const int rc = jit_launch(p, "mc::k_mh<" + std::to_string(WPC) + ", " +
-                                         (LDS ? "true" : "false") + ", true>",
-                                  (unsigned)grid, block_of(WPC), lds, st, args, &used);
-        if (rc != MC_OK || used) return rc;
-    }
-    MC_HIP_TRY(allow_lds(k_mh<WPC, LDS, EX>, lds));
-    hipLaunchKernelGGL((k_mh<WPC, LDS, EX>), dim3((unsigned)grid), dim3(block_of(WPC)), lds, st,
-                       ctx_of(p), A, scale, (mc_chain_scalars*)b, (float*)(b + qo), samples,
-                       trace_of(tr), ws);
-    MC_HIP_TRY(hipGetLastError());
-    return MC_OK;
+    // (EX: the program's expression terms compiled, jit.hip)
+    const std::string jit = !EX ? "" : "mc::k_mh<" + std::to_string(WPC) + ", " +
+                                           (LDS ? "true" : "false") + ", true>";
+    return launch_tape(p, k_mh<WPC, LDS, EX>, jit, grid, block_of(WPC), lds, st, ctx_of(p), R.A,
+                       scale, R.scalars, R.q, samples, trace_of(tr), ws);
 }
 
 extern "C" int mc_mh_run(const mc_program* p, const mc_run_config* cfg, double proposal_scale,

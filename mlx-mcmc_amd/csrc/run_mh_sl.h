@@ -14,10 +14,7 @@ inline int64_t mh_sl_line_bytes(const mc_program* p, int64_t C) {
 // or the slice kernel is forced to the interpreter.
 inline int g_mh_sliced = -1;
 inline bool mh_sliced_enabled() {
-    if (g_mh_sliced < 0) {
-        const char* e = std::getenv("MC_MH_SLICED");
-        g_mh_sliced = (e && e[0] == '0') ? 0 : 1;
-    }
+    if (g_mh_sliced < 0) g_mh_sliced = env_on("MC_MH_SLICED");
     return g_mh_sliced == 1;
 }
 // (a program with expression terms, LanePlan::nuts_expr: the JIT-compiled
@@ -27,8 +24,7 @@ inline bool use_mh_sliced(const mc_program* p) {
     return mh_sliced_enabled() && p->sl.S >= 2 && p->lr.ok && (p->lr.fast || expr) &&
            lanes_fast_enabled() &&
            p->lr.S >= 2 && p->lr.S <= kLrSlices && p->slice_kernel != 1 &&
-           (size_t)p->lr.sdata_floats * 4 + p->lr.sterms.size() * sizeof(LrSterm) <=
-               (size_t)kSlLdsBudget;
+           lr_base_lds_bytes(p) <= (size_t)kSlLdsBudget;
 }
 inline int64_t mh_sl_workspace_bytes(const mc_program* p, int64_t C) {
     return kSlStatusBytes + mh_sl_line_bytes(p, C);

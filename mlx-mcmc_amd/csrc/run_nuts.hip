@@ -1,7 +1,6 @@
 // run_nuts.hip — NUTS launches (k_nuts_lr, k_nuts) and mc_nuts_run.
 #include "run_nuts_sl.h"
 #include "run_nuts_lr_met.h"
-#include "jit.h"
 
 
 // LDS floats per chain group of k_nuts: group scratch, pending words and,
@@ -31,24 +30,19 @@ extern "C" int64_t mc_nuts_workspace_bytes(const mc_program* p, int64_t C, int32
 // MET: the metric instantiation (metric.h) on the buffer `metric`; minv and
 // msqrt follow the arena in LDS when the two extra vectors still fit its budget
 // (the arena decision itself, and so the workspace, is the one without a metric)
-template <int WPC, bool LDS, bool EX, bool MET = false>
+template <int WPC, bool LDS, bool EX, bool MET>
 static int launch_nuts(const mc_program* p, const mc_run_config* cfg, void* state,
-                       float* samples, const mc_trace* tr, float* ws, hipStream_t st,
-                       void* metric = nullptr, int adapt = 0) {
-    int64_t qo, go;
-    mc_state_offsets(p, cfg->num_chains, &qo, &go);
-    char* b = (char*)state;
-    RunArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.cfg = *cfg;
+                       float* samples, const mc_trace* tr, float* ws, hipStream_t st, void* metric,
+                       int adapt) {
+    RunState R = run_state(p, cfg, state);
+    RunArgs& A = R.A;
     A.dpad = dpad_of(p->D);
     A.scratch_floats = scratch_of(p);
     A.lds_floats = (int32_t)nuts_lds_floats(p, cfg->max_tree_depth, LDS);
-    MetricDev M = {};
+    bool ml = false;
     if constexpr (MET) {
-        const bool ml = LDS && cpb_of(WPC) * (A.lds_floats + 2 * (int64_t)A.dpad) * 4 <= kNutsLdsBudget;
+        ml = LDS && cpb_of(WPC) * (A.lds_floats + 2 * (int64_t)A.dpad) * 4 <= kNutsLdsBudget;
         if (ml) A.lds_floats += 2 * A.dpad;
-        M = metricdev_of(p, cfg->num_chains, metric, adapt, ml);
     }
     size_t lds = (size_t)cpb_of(WPC) * A.lds_floats * 4;
     // the data pool after the chain groups when it fits as well
@@ -62,33 +56,20 @@ static int launch_nuts(const mc_program* p, const mc_run_config* cfg, void* stat
     // the program's expression terms compiled (jit.hip), with at most the
     // default 64 KB of dynamic LDS (module kernels launch without the
     // attribute allow_lds sets)
-    if (EX && lds <= 64 * 1024) {
-        DevCtx ctx = ctx_of(p);
-        mc_chain_scalars* scal = (mc_chain_scalars*)b;
-        float *sq = (float*)(b + qo), *sg = (float*)(b + go);
-        TraceDev td = trace_of(tr);
-        void* args[] = {&ctx, &A, &scal, &sq, &sg, &samples, &td, &ws, &M};  // (M: MET only)
-        bool used = false;
-        const int rc = jit_launch(p, "mc::k_nuts<" + std::to_string(WPC) + ", " +
-                                         (LDS ? "true" : "false") +
-                                         (MET ? ", true, true, mc::MetricDev>" : ", true>"),
-                                  (unsigned)grid, block_of(WPC), lds, st, args, &used);
-        if (rc != MC_OK || used) return rc;
-    }
-    if constexpr (MET) {
-        auto kern = k_nuts<WPC, LDS, EX, true, MetricDev>;
-        MC_HIP_TRY(allow_lds(kern, lds));
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block_of(WPC)), lds, st, ctx_of(p), A,
-                           (mc_chain_scalars*)b, (float*)(b + qo), (float*)(b + go), samples,
-                           trace_of(tr), ws, M);
-    } else {
-        MC_HIP_TRY(allow_lds(k_nuts<WPC, LDS, EX>, lds));
-        hipLaunchKernelGGL((k_nuts<WPC, LDS, EX>), dim3((unsigned)grid), dim3(block_of(WPC)), lds,
-                           st, ctx_of(p), A, (mc_chain_scalars*)b, (float*)(b + qo),
-                           (float*)(b + go), samples, trace_of(tr), ws);
-    }
-    MC_HIP_TRY(hipGetLastError());
-    return MC_OK;
+    const std::string jit = !(EX && lds <= 64 * 1024)
+                                ? ""
+                                : "mc::k_nuts<" + std::to_string(WPC) + ", " +
+                                      (LDS ? "true" : "false") +
+                                      (MET ? ", true, true, mc::MetricDev>" : ", true>");
+    auto go = [&](auto kern, auto... met) {
+        return launch_tape(p, kern, jit, grid, block_of(WPC), lds, st, ctx_of(p), A, R.scalars,
+                           R.q, R.g, samples, trace_of(tr), ws, met...);
+    };
+    if constexpr (MET)
+        return go(k_nuts<WPC, LDS, EX, true, MetricDev>,
+                  metricdev_of(p, cfg->num_chains, metric, adapt, ml));
+    else
+        return go(k_nuts<WPC, LDS, EX>);
 }
 
 // The lane-resident NUTS kernel (nuts_lanes.h) for programs planned as one
@@ -97,15 +78,11 @@ static int launch_nuts(const mc_program* p, const mc_run_config* cfg, void* stat
 // arena does not fit the LDS budget.
 static bool nuts_lanes_enabled() {
     static int on = -1;
-    if (on < 0) {
-        const char* e = std::getenv("MC_NUTS_LANES");
-        on = (e && e[0] == '0') ? 0 : 1;
-    }
+    if (on < 0) on = env_on("MC_NUTS_LANES");
     return on == 1;
 }
 static size_t nuts_lr_lds_bytes(const mc_program* p, int max_depth) {
-    return (size_t)p->lr.sdata_floats * 4 + p->lr.sterms.size() * sizeof(LrSterm) +
-           (size_t)nuts_lr_arena_floats(p->lr.rs, max_depth) * 4;
+    return lr_base_lds_bytes(p) + (size_t)nuts_lr_arena_floats(p->lr.rs, max_depth) * 4;
 }
 static bool use_nuts_lanes(const mc_program* p, int max_depth) {
     return nuts_lanes_enabled() && p->sl.S < 2 && p->lr.ok && p->lr.S == 1 && !p->lr.has_xf &&
@@ -161,11 +138,16 @@ extern "C" int mc_debug_nuts_sliced(int on) {
 // k_nuts_lr's draw wave for the register-only variant: MC_NUTS_DRAW_WAVE=0 in
 // the environment keeps one wave per chain (A/B)
 static bool nuts_draw_wave_enabled() {
-    static const int on = [] {
-        const char* e = std::getenv("MC_NUTS_DRAW_WAVE");
-        return (e && e[0] == '0') ? 0 : 1;
-    }();
-    return on == 1;
+    static const bool on = env_on("MC_NUTS_DRAW_WAVE");
+    return on;
+}
+// LDS bytes, the draw wave (nuts_lanes.h PW: when its buffers fit) and the
+// threads of a k_nuts_lr workgroup
+static NutsLrShape nuts_lr_launch_shape(const mc_program* p, int max_depth) {
+    const size_t lds = nuts_lr_lds_bytes(p, max_depth);
+    const size_t lds_pw = lds + (size_t)nuts_lr_draw_words(max_depth) * 4;
+    const bool pw = nuts_draw_wave_enabled() && max_depth <= 12 && lds_pw <= (size_t)kSlLdsBudget;
+    return NutsLrShape{pw ? lds_pw : lds, pw, pw ? 128 : 64};
 }
 
 static int g_nuts_variant = -1;  // mc_debug_nuts_variant
@@ -177,44 +159,55 @@ extern "C" int mc_debug_nuts_variant(int variant) {
 template <int RS, int NSH>
 static int launch_nuts_lr(const mc_program* p, const mc_run_config* cfg, void* state,
                           float* samples, const mc_trace* tr, hipStream_t st) {
-    int64_t qo, go;
-    mc_state_offsets(p, cfg->num_chains, &qo, &go);
-    char* b = (char*)state;
-    RunArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.cfg = *cfg;
-    size_t lds = nuts_lr_lds_bytes(p, cfg->max_tree_depth);
-    // the draw wave (nuts_lanes.h PW) when its buffers fit
-    const size_t lds_pw = lds + (size_t)nuts_lr_draw_words(cfg->max_tree_depth) * 4;
-    const bool pw = nuts_draw_wave_enabled() && cfg->max_tree_depth <= 12 &&
-                    lds_pw <= (size_t)kSlLdsBudget;
+    RunState R = run_state(p, cfg, state);
+    const NutsLrShape sh = nuts_lr_launch_shape(p, cfg->max_tree_depth);
+    const bool pw = sh.pw;
     auto kern = lanes_specialised(p) ? (pw ? k_nuts_lr<RS, NSH, 1, true> : k_nuts_lr<RS, NSH, 1>)
                                      : (pw ? k_nuts_lr<RS, NSH, 0, true> : k_nuts_lr<RS, NSH, 0>);
     if constexpr (NSH == 3)
         if (lanes_register_only(p) && g_nuts_variant < 0)
             kern = pw ? k_nuts_lr<RS, NSH, 2, true> : k_nuts_lr<RS, NSH, 2>;
     if (g_nuts_variant == 0) kern = pw ? k_nuts_lr<RS, NSH, 0, true> : k_nuts_lr<RS, NSH, 0>;
-    if (pw) lds = lds_pw;
-    const int threads = pw ? 128 : 64;
-    MC_HIP_TRY(allow_lds(kern, lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)cfg->num_chains), dim3(threads), lds, st, lrctx_of(p), A,
-                       (mc_chain_scalars*)b, (float*)(b + qo), (float*)(b + go), samples,
-                       trace_of(tr));
-    MC_HIP_TRY(hipGetLastError());
+    return launch_tape(p, kern, "", cfg->num_chains, sh.threads, sh.lds, st, lrctx_of(p), R.A,
+                       R.scalars, R.q, R.g, samples, trace_of(tr));
+}
+
+// What the three NUTS entries check first (met: the metric entries)
+static int nuts_validate(const mc_program* p, const mc_run_config* cfg, void* state, bool met,
+                         const void* metric) {
+    int rc = check_cfg(p, cfg, state);
+    if (rc) return rc;
+    if (met && !metric) return fail(MC_ERR_INVALID, "metric buffer is NULL");
+    if (cfg->max_tree_depth < 0 || cfg->max_tree_depth > kMaxTreeDepth)
+        return fail(MC_ERR_UNSUPPORTED, "max_tree_depth must be in [0, %d]", kMaxTreeDepth);
     return MC_OK;
+}
+// (mc_nuts_run's contract, for every entry: what mc_nuts_workspace_bytes asks for)
+static int nuts_check_workspace(const mc_program* p, const mc_run_config* cfg, const void* ws,
+                                int64_t ws_bytes) {
+    const int64_t need = mc_nuts_workspace_bytes(p, cfg->num_chains, cfg->max_tree_depth);
+    if (need > 0 && (ws == nullptr || ws_bytes < need))
+        return fail(MC_ERR_INVALID, "workspace too small: need %lld bytes", (long long)need);
+    return MC_OK;
+}
+// ... and where mc_nuts_run and mc_nuts_run_metric end: k_nuts on the tape
+template <bool MET>
+static int nuts_tape(const mc_program* p, const mc_run_config* cfg, void* state, float* samples,
+                     const mc_trace* tr, void* ws, hipStream_t st, void* metric, int adapt) {
+    const bool lds = nuts_use_lds(p, cfg->max_tree_depth);
+    return dispatch_tape(p, lds, [&](auto W, auto L, auto E) {
+        return launch_nuts<decltype(W)::value, decltype(L)::value, decltype(E)::value, MET>(
+            p, cfg, state, samples, tr, (float*)ws, st, metric, adapt);
+    });
 }
 
 extern "C" int mc_nuts_run(const mc_program* p, const mc_run_config* cfg, void* state,
                            float* samples, const mc_trace* tr, void* ws, int64_t ws_bytes,
                            void* stream) {
-    int rc = check_cfg(p, cfg, state);
+    int rc = nuts_validate(p, cfg, state, false, nullptr);
     if (rc) return rc;
-    if (cfg->max_tree_depth < 0 || cfg->max_tree_depth > kMaxTreeDepth)
-        return fail(MC_ERR_UNSUPPORTED, "max_tree_depth must be in [0, %d]", kMaxTreeDepth);
     if (cfg->num_chains == 0 || cfg->iter_count == 0) return MC_OK;
-    const int64_t need = mc_nuts_workspace_bytes(p, cfg->num_chains, cfg->max_tree_depth);
-    if (need > 0 && (ws == nullptr || ws_bytes < need))
-        return fail(MC_ERR_INVALID, "workspace too small: need %lld bytes", (long long)need);
+    if ((rc = nuts_check_workspace(p, cfg, ws, ws_bytes))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (use_nuts_sliced(p, cfg->max_tree_depth)) {
         // (tags continue on this workspace: no ws_forget, nuts_sliced.h)
@@ -227,50 +220,28 @@ extern "C" int mc_nuts_run(const mc_program* p, const mc_run_config* cfg, void* 
         // (expression terms without their compiled kernel: the tape below)
     }
     if (ws) ws_forget(ws);  // another kernel's data: a later sliced launch clears it
-    if (use_nuts_lanes(p, cfg->max_tree_depth)) {
-        const bool n4 = p->lr.Dsh > 3;
-        switch (p->lr.rs) {
-            case 1: return n4 ? launch_nuts_lr<1, 4>(p, cfg, state, samples, tr, st)
-                              : launch_nuts_lr<1, 3>(p, cfg, state, samples, tr, st);
-            case 2: return n4 ? launch_nuts_lr<2, 4>(p, cfg, state, samples, tr, st)
-                              : launch_nuts_lr<2, 3>(p, cfg, state, samples, tr, st);
-            default: return n4 ? launch_nuts_lr<4, 4>(p, cfg, state, samples, tr, st)
-                               : launch_nuts_lr<4, 3>(p, cfg, state, samples, tr, st);
-        }
-    }
-    float* w = (float*)ws;
-    const bool lds = nuts_use_lds(p, cfg->max_tree_depth);
-    return dispatch_tape(p, lds, [&](auto W, auto L, auto E) {
-        return launch_nuts<decltype(W)::value, decltype(L)::value, decltype(E)::value>(
-            p, cfg, state, samples, tr, w, st);
-    });
+    if (use_nuts_lanes(p, cfg->max_tree_depth))
+        return dispatch_lanes(p, [&](auto RS, auto NSH) {
+            return launch_nuts_lr<decltype(RS)::value, decltype(NSH)::value>(p, cfg, state,
+                                                                             samples, tr, st);
+        });
+    return nuts_tape<false>(p, cfg, state, samples, tr, ws, st, nullptr, 0);
 }
 
 extern "C" int mc_nuts_run_metric(const mc_program* p, const mc_run_config* cfg, void* state,
                                   float* samples, const mc_trace* tr, void* ws, int64_t ws_bytes,
                                   void* metric, int32_t adapt, void* stream) {
-    int rc = check_cfg(p, cfg, state);
+    int rc = nuts_validate(p, cfg, state, true, metric);
     if (rc) return rc;
-    if (!metric) return fail(MC_ERR_INVALID, "metric buffer is NULL");
-    if (cfg->max_tree_depth < 0 || cfg->max_tree_depth > kMaxTreeDepth)
-        return fail(MC_ERR_UNSUPPORTED, "max_tree_depth must be in [0, %d]", kMaxTreeDepth);
     if (use_nuts_sliced(p, cfg->max_tree_depth) || use_nuts_lanes(p, cfg->max_tree_depth))
         return fail(MC_ERR_UNSUPPORTED,
                     "a metric runs on the chain-per-workgroup kernel k_nuts only and this program "
                     "is planned onto a sliced or lane-resident kernel: "
                     "mc_program_set_slices(prog, 1) keeps it on k_nuts");
     if (cfg->num_chains == 0 || cfg->iter_count == 0) return MC_OK;
-    const int64_t need = mc_nuts_workspace_bytes(p, cfg->num_chains, cfg->max_tree_depth);
-    if (need > 0 && (ws == nullptr || ws_bytes < need))
-        return fail(MC_ERR_INVALID, "workspace too small: need %lld bytes", (long long)need);
+    if ((rc = nuts_check_workspace(p, cfg, ws, ws_bytes))) return rc;
     if (ws) ws_forget(ws);
-    float* w = (float*)ws;
-    hipStream_t st = (hipStream_t)stream;
-    const bool lds = nuts_use_lds(p, cfg->max_tree_depth);
-    return dispatch_tape(p, lds, [&](auto W, auto L, auto E) {
-        return launch_nuts<decltype(W)::value, decltype(L)::value, decltype(E)::value, true>(
-            p, cfg, state, samples, tr, w, st, metric, adapt);
-    });
+    return nuts_tape<true>(p, cfg, state, samples, tr, ws, (hipStream_t)stream, metric, adapt);
 }
 
 // Why mc_nuts_run_metric_lanes declines this program (nullptr: it runs it)
@@ -298,26 +269,15 @@ extern "C" int mc_nuts_run_metric_lanes(const mc_program* p, const mc_run_config
                                         float* samples, const mc_trace* tr, void* ws,
                                         int64_t ws_bytes, void* metric, int32_t adapt,
                                         void* stream) {
-    int rc = check_cfg(p, cfg, state);
+    int rc = nuts_validate(p, cfg, state, true, metric);
     if (rc) return rc;
-    if (!metric) return fail(MC_ERR_INVALID, "metric buffer is NULL");
-    if (cfg->max_tree_depth < 0 || cfg->max_tree_depth > kMaxTreeDepth)
-        return fail(MC_ERR_UNSUPPORTED, "max_tree_depth must be in [0, %d]", kMaxTreeDepth);
     if (const char* why = nuts_metric_lanes_why(p, cfg->max_tree_depth))
         return nuts_metric_lanes_refuse(why);
     if (cfg->num_chains == 0 || cfg->iter_count == 0) return MC_OK;
-    // (mc_nuts_run's contract: what mc_nuts_workspace_bytes asks for, unused here)
-    const int64_t need = mc_nuts_workspace_bytes(p, cfg->num_chains, cfg->max_tree_depth);
-    if (need > 0 && (ws == nullptr || ws_bytes < need))
-        return fail(MC_ERR_INVALID, "workspace too small: need %lld bytes", (long long)need);
+    if ((rc = nuts_check_workspace(p, cfg, ws, ws_bytes))) return rc;  // (unused here)
     if (ws) ws_forget(ws);
-    // LDS and the draw wave as launch_nuts_lr decides them
-    const size_t lds = nuts_lr_lds_bytes(p, cfg->max_tree_depth);
-    const size_t lds_pw = lds + (size_t)nuts_lr_draw_words(cfg->max_tree_depth) * 4;
-    const bool pw = nuts_draw_wave_enabled() && cfg->max_tree_depth <= 12 &&
-                    lds_pw <= (size_t)kSlLdsBudget;
-    return nuts_lr_met_launch(p, cfg, state, samples, tr, metric, adapt, pw ? lds_pw : lds, pw,
-                              (hipStream_t)stream);
+    return nuts_lr_met_launch(p, cfg, state, samples, tr, metric, adapt,
+                              nuts_lr_launch_shape(p, cfg->max_tree_depth), (hipStream_t)stream);
 }
 
 #ifdef MC_STAMPS

@@ -3,8 +3,7 @@
 // run_nuts_sl_rt.hip (the run-time form): two translation units so the
 // instantiations compile in parallel.
 #pragma once
-#include "host.h"
-#include "jit.h"
+#include "launch.h"
 
 // chains (waves) per workgroup of k_nuts_sl
 constexpr int kNslWaves = 8;
@@ -12,7 +11,7 @@ constexpr int kNslWaves = 8;
 // LDS bytes of a k_nuts_sl workgroup: the slice block and scalar terms, then
 // per wave the first-leaf arena and the shared parameters' arena rows
 inline size_t nuts_sl_lds_bytes(const mc_program* p, int max_depth) {
-    return (size_t)p->lr.sdata_floats * 4 + p->lr.sterms.size() * sizeof(LrSterm) +
+    return lr_base_lds_bytes(p) +
            (size_t)kNslWaves *
                ((size_t)nuts_sl_first_floats(p->lr.rs, max_depth) +
                 (size_t)nuts_sl_shared_rows(max_depth) * 4) * 4;
@@ -40,6 +39,38 @@ inline int64_t nuts_sl_line_bytes(const mc_program* p, int64_t C) {
            groups * (int64_t)p->lr.S * 16 * 8;
 }
 
+// The launches of kernel pair k
+template <typename K>
+inline int nuts_sl_exchange(const char* name, K& k, const mc_program* p, const mc_run_config* cfg,
+                            void* state, float* samples, const mc_trace* tr, void* ws,
+                            hipStream_t st) {
+    RunState R = run_state(p, cfg, state);
+    const LrCtx ctx = lrctx_of(p);
+    const TraceDev td = trace_of(tr);
+    const int maxj = cfg->max_tree_depth;
+    const int64_t lines = nuts_sl_line_bytes(p, cfg->num_chains);
+    ExchangeLaunch d;
+    d.name = name;
+    d.threads = 64 * kNslWaves;
+    d.chains = kNslWaves;
+    d.S = p->lr.S;
+    d.lds = nuts_sl_lds_bytes(p, maxj);
+    d.blocks_per_launch = 0;  // what the device holds: the workspace has lines for every block
+    d.clear_bytes = kSlStatusBytes + lines;
+    // tags: one per leaf, at most iter_count * 2^maxj leaves per chain
+    d.tags_per_launch = (uint64_t)cfg->iter_count * (1ull << maxj) + 1;
+    d.restart_tags = false;
+    d.coresident = true;
+    int* status = (int*)ws;
+    unsigned long long* xch = (unsigned long long*)((char*)ws + kSlStatusBytes);
+    float* pool = (float*)((char*)ws + kSlStatusBytes + lines);
+    return run_exchange(d, k, cfg->num_chains, ws, st, R.A,
+                        [&](int64_t g0, int64_t ng, int64_t grid, bool xl, uint32_t base) {
+        return k.launch(xl, grid, d.threads, d.lds, st, ctx, R.A, g0 * kNslWaves, ng, R.scalars,
+                        R.q, R.g, samples, td, xch, pool, status, base);
+    });
+}
+
 template <int RS, int NSH, int OCC, int FORM>
 inline int launch_nuts_sl(const mc_program* p, const mc_run_config* cfg, void* state,
                           float* samples, const mc_trace* tr, void* ws, hipStream_t st) {
@@ -47,49 +78,8 @@ inline int launch_nuts_sl(const mc_program* p, const mc_run_config* cfg, void* s
     // the compile-time form also with L2-resident records (host.h xcd_round_robin)
     auto kern_xl = kern;
     if constexpr (FORM >= 0) kern_xl = k_nuts_sl<RS, NSH, kNslWaves, OCC, FORM, true>;
-    int64_t qo, go;
-    mc_state_offsets(p, cfg->num_chains, &qo, &go);
-    char* b = (char*)state;
-    RunArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.cfg = *cfg;
-    const LrCtx ctx = lrctx_of(p);
-    const int maxj = cfg->max_tree_depth;
-    const size_t lds = nuts_sl_lds_bytes(p, maxj);
-    MC_HIP_TRY(allow_lds(kern, lds));
-    if (kern_xl != kern) MC_HIP_TRY(allow_lds(kern_xl, lds));
-    const int64_t C = cfg->num_chains;
-    const int64_t groups = (C + kNslWaves - 1) / kNslWaves;
-    const int S = p->lr.S;
-    const int64_t cap = resident_capacity(kern, 64 * kNslWaves, lds);
-    if (cap < S)
-        return fail(MC_ERR_UNSUPPORTED,
-                    "sliced NUTS: a chain block's %d workgroups must be co-resident, the device "
-                    "holds %lld of this kernel", S, (long long)cap);
-    const int64_t gpl = std::min(groups, cap / S);
-    const int64_t lines = nuts_sl_line_bytes(p, C);
-    int* status = (int*)ws;
-    unsigned long long* xch = (unsigned long long*)((char*)ws + kSlStatusBytes);
-    float* pool = (float*)((char*)ws + kSlStatusBytes + lines);
-    A.fault = g_exchange_fault;
-    // tags: one per leaf, at most iter_count * 2^maxj leaves per chain
-    const uint64_t per_launch = (uint64_t)cfg->iter_count * (1ull << maxj) + 1;
-    const int64_t nlaunch = (groups + gpl - 1) / gpl;
-    uint32_t base = 0;
-    if (ws_reserve(ws, per_launch * (uint64_t)nlaunch, (uint64_t)(kSlStatusBytes + lines), &base))
-        MC_HIP_TRY(hipMemsetAsync(ws, 0, kSlStatusBytes + lines, st));
-    ws_mark_status(ws);
-    for (int64_t g0 = 0; g0 < groups; g0 += gpl) {
-        const int64_t ng = std::min(gpl, groups - g0);
-        const bool xl = kern_xl != kern && xcd_round_robin(ng * S, S);
-        const hipError_t e = launch_exchange(
-            xl ? kern_xl : kern, ng * S, 64 * kNslWaves, lds, st, ctx, A, g0 * kNslWaves, ng,
-            (mc_chain_scalars*)b, (float*)(b + qo), (float*)(b + go), samples, trace_of(tr), xch,
-            pool, status, base);
-        MC_HIP_TRY(e);
-        base += (uint32_t)per_launch;
-    }
-    return MC_OK;
+    auto k = static_pair(kern, kern_xl);
+    return nuts_sl_exchange("sliced NUTS", k, p, cfg, state, samples, tr, ws, st);
 }
 
 // The run-time form compiled with the program's expression terms (jit.hip):
@@ -98,66 +88,12 @@ inline int launch_nuts_sl(const mc_program* p, const mc_run_config* cfg, void* s
 template <int RS, int NSH, int OCC>
 inline int launch_nuts_sl_jit(const mc_program* p, const mc_run_config* cfg, void* state,
                               float* samples, const mc_trace* tr, void* ws, hipStream_t st) {
-    const std::string name = "mc::k_nuts_sl<" + std::to_string(RS) + ", " + std::to_string(NSH) +
-                             ", " + std::to_string(kNslWaves) + ", " + std::to_string(OCC) + ", -1";
-    hipFunction_t f = nullptr, fxl = nullptr;
-    int rc = jit_function(p, name + ", false>", &f);
+    ModulePair k{p, "mc::k_nuts_sl<" + std::to_string(RS) + ", " + std::to_string(NSH) + ", " +
+                        std::to_string(kNslWaves) + ", " + std::to_string(OCC) + ", -1"};
+    const int rc = k.load();
     if (rc != MC_OK) return rc;
-    if (f == nullptr) return kLanesNoJit;
-    int64_t qo, go;
-    mc_state_offsets(p, cfg->num_chains, &qo, &go);
-    char* b = (char*)state;
-    RunArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.cfg = *cfg;
-    LrCtx ctx = lrctx_of(p);
-    const int maxj = cfg->max_tree_depth;
-    const size_t lds = nuts_sl_lds_bytes(p, maxj);
-    const int64_t C = cfg->num_chains;
-    const int64_t groups = (C + kNslWaves - 1) / kNslWaves;
-    const int S = p->lr.S;
-    int n = 0;
-    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 64 * kNslWaves, lds) !=
-        hipSuccess)
-        n = 0;
-    const int64_t cap = (int64_t)n * device_cus();
-    if (cap < S)
-        return fail(MC_ERR_UNSUPPORTED,
-                    "sliced NUTS (expression JIT): a chain block's %d workgroups must be "
-                    "co-resident, the device holds %lld of this kernel", S, (long long)cap);
-    const int64_t gpl = std::min(groups, cap / S);
-    const int64_t lines = nuts_sl_line_bytes(p, C);
-    int* status = (int*)ws;
-    unsigned long long* xch = (unsigned long long*)((char*)ws + kSlStatusBytes);
-    float* pool = (float*)((char*)ws + kSlStatusBytes + lines);
-    A.fault = g_exchange_fault;
-    const uint64_t per_launch = (uint64_t)cfg->iter_count * (1ull << maxj) + 1;
-    const int64_t nlaunch = (groups + gpl - 1) / gpl;
-    uint32_t base = 0;
-    if (ws_reserve(ws, per_launch * (uint64_t)nlaunch, (uint64_t)(kSlStatusBytes + lines), &base))
-        MC_HIP_TRY(hipMemsetAsync(ws, 0, kSlStatusBytes + lines, st));
-    ws_mark_status(ws);
-    mc_chain_scalars* scal = (mc_chain_scalars*)b;
-    float *sq = (float*)(b + qo), *sg = (float*)(b + go);
-    TraceDev td = trace_of(tr);
-    for (int64_t g0 = 0; g0 < groups; g0 += gpl) {
-        int64_t ng = std::min(gpl, groups - g0);
-        int64_t cb = g0 * kNslWaves;
-        hipFunction_t k = f;
-        if (xcd_round_robin(ng * S, S)) {
-            if (fxl == nullptr) {
-                rc = jit_function(p, name + ", true>", &fxl);
-                if (rc != MC_OK) return rc;
-            }
-            if (fxl != nullptr) k = fxl;
-        }
-        void* args[] = {&ctx, &A, &cb, &ng, &scal, &sq, &sg, &samples, &td, &xch, &pool, &status,
-                        &base};
-        MC_HIP_TRY(hipModuleLaunchKernel(k, (unsigned)(ng * S), 1, 1, 64 * kNslWaves, 1, 1,
-                                         (unsigned)lds, st, args, nullptr));
-        base += (uint32_t)per_launch;
-    }
-    return MC_OK;
+    if (k.f == nullptr) return kLanesNoJit;
+    return nuts_sl_exchange("sliced NUTS (expression JIT)", k, p, cfg, state, samples, tr, ws, st);
 }
 
 // the compile-time hierarchical form (run_nuts_sl.hip) and the run-time form
@@ -174,10 +110,7 @@ int nuts_sl_rt(const mc_program* p, const mc_run_config* cfg, void* state, float
 // max_tree_depth is outside [1, kNslMaxDepth] or the LDS arenas do not fit.
 inline int g_nuts_sliced = -1;  // mc_debug_nuts_sliced; -1: MC_NUTS_SLICED
 inline bool nuts_sliced_enabled() {
-    if (g_nuts_sliced < 0) {
-        const char* e = std::getenv("MC_NUTS_SLICED");
-        g_nuts_sliced = (e && e[0] == '0') ? 0 : 1;
-    }
+    if (g_nuts_sliced < 0) g_nuts_sliced = env_on("MC_NUTS_SLICED");
     return g_nuts_sliced == 1;
 }
 // A program with expression terms (LanePlan::nuts_expr) runs the JIT-compiled

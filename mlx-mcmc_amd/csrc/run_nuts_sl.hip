@@ -8,13 +8,12 @@ int nuts_sl_hier(const mc_program* p, const mc_run_config* cfg, void* state, flo
     constexpr int HIER = LF_SW | LF_SWS | LF_DIR | LF_DM | LF_DS;
     constexpr int NSH = lf_nroles(HIER);
     const bool o4 = nuts_sl_occ(p) == 4;
-    switch (p->lr.rs) {
-        case 1: return o4 ? launch_nuts_sl<1, NSH, 4, HIER>(p, cfg, state, samples, tr, ws, st)
-                          : launch_nuts_sl<1, NSH, 2, HIER>(p, cfg, state, samples, tr, ws, st);
-        case 2: return o4 ? launch_nuts_sl<2, NSH, 4, HIER>(p, cfg, state, samples, tr, ws, st)
-                          : launch_nuts_sl<2, NSH, 2, HIER>(p, cfg, state, samples, tr, ws, st);
-        default: return launch_nuts_sl<4, NSH, 2, HIER>(p, cfg, state, samples, tr, ws, st);
-    }
+    return dispatch_rs(p, [&](auto R) {
+        constexpr int RS = decltype(R)::value;
+        if constexpr (RS < 4)  // (4 slots per lane: no 4 waves per SIMD, <= 128 VGPRs)
+            if (o4) return launch_nuts_sl<RS, NSH, 4, HIER>(p, cfg, state, samples, tr, ws, st);
+        return launch_nuts_sl<RS, NSH, 2, HIER>(p, cfg, state, samples, tr, ws, st);
+    });
 }
 
 #ifdef MC_STAMPS
