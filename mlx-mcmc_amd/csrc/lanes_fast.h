@@ -26,9 +26,16 @@
 //   * both chains' per-step arithmetic runs packed (v_pk_*_f32: the same
 //     IEEE operations per chain, two chains per instruction), the per-launch
 //     uniform values pinned in VGPRs (no SGPR spills reloaded per step);
-//   * the moment sweep keeps even and odd elements in separate packed
-//     accumulators (two dependency chains each; a dependent v_pk_add_f32
-//     advances every 10 cycles, scripts/micro/pk_probe.hip);
+//   * the moment sweep sums the second moment alone, even and odd elements in
+//     separate packed accumulators (two dependency chains; a dependent
+//     v_pk_fma_f32 advances every 10 cycles, scripts/micro/pk_probe.hip): per
+//     element and chain pair d = x - th and one fma.  The first moment
+//     sum (x - th) is linear in th: about a centre c it is
+//     sum (x - c) + n (c - th), and the data's share — c, the run's mean, and
+//     R = sum (x - c) — is formed once per launch (lf_run_consts: float64 sums
+//     in element order, rounded once), so a step forms M1 = fma(n, c - th, R)
+//     (lf_m1) instead of adding every element again: a regrouping of the same
+//     sum, with three roundings where the serial sum had one per element;
 //   * the wave totals of the record are reduce-scattered (permlane32 /
 //     permlane16 swaps + one 16-lane DPP row sum) so that pair P's total is
 //     in row perm[P % 4] of register P / 4 — no readlanes, no publish select;
@@ -150,34 +157,70 @@ MC_DEV f2 lf_hi_minus(f2 xy, f2 th) {
     return d;
 }
 
-// Moment sums of one lane's run (value = data x, loc = the lane's private
-// parameter th) for both chains, packed FP32: d = x - th, s1 += d,
+// The data's share of a run's first moment, once per launch: the sweep's
+// M1 = sum_e (x_e - th) is linear in th, and regrouped about a centre c it is
+// sum_e (x_e - c) + n (c - th) = R + n (c - th): R and c depend on the run's
+// observations alone.  c = (float) mean(x), R = (float) sum_e (x_e - c), both
+// sums in double and in element order (group g of the run is the float4 at
+// xv + 256 g; the tile is padded to whole groups, so every load is in bounds);
+// an empty run has c = R = 0.  Returns (c, R).  Centred, because
+// sum x - n th would cancel at the observations' magnitude; this form
+// carries three roundings (c - th, the fma, R) where the serial sum carried
+// one per element.
+MC_DEV f2 lf_run_consts(const float* xv, int len) {
+    const int ng = (len + 3) >> 2;
+    auto total = [&](double c) {
+        double s = 0.0;
+#pragma unroll 4
+        for (int g = 0; g < ng; ++g) {
+            const float4 a = *(const float4*)(xv + g * 256);
+            const float x[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (4 * g + k < len) s += (double)x[k] - c;
+        }
+        return s;
+    };
+    if (len <= 0) return (f2){0.f, 0.f};
+    const float c = (float)(total(0.0) / (double)len);
+    return (f2){c, (float)total((double)c)};
+}
+
+// M1 of a run from its launch constants c and R (lf_run_consts), its element
+// count cnt (both chains) and the position th: fma(cnt, c - th, R), per
+// chain.  Not packed: c and R are one register each, and packed operands
+// would want them broadcast in aligned register pairs kept for the whole
+// launch — two registers more than the kernel of the Large shape has without
+// spilling; the two chains' subtract and fma are four instructions a step.
+MC_DEV f2 lf_m1(f2 cnt, float c, float R, f2 th) {
+    return (f2){__builtin_fmaf(cnt[0], c - th[0], R), __builtin_fmaf(cnt[1], c - th[1], R)};
+}
+
+// Second-moment sum of one lane's run (value = data x, loc = the lane's
+// private parameter th) for both chains, packed FP32: d = x - th,
 // s2 = fma(d, d, s2), with the even and odd elements in separate packed
-// accumulators (two independent dependency chains each).
+// accumulators (two independent dependency chains).  (The first moment needs
+// no sweep: lf_m1.)
 // REREAD (one register slot, where the bounds are in SGPRs): the uniform
 // bounds are opaque per sweep, so the trip conditions derived from them are
 // scalar compares at their use (SCC), not per-launch lane masks that occupy
 // SGPR pairs and spill (a v_readlane per use in the step loop).
 template <bool REREAD = false>
-MC_DEV void lf_moments(const float* xv, int len, int lmin4, int lmax, f2 th, f2& s1, f2& s2) {
+MC_DEV void lf_moments(const float* xv, int len, int lmin4, int lmax, f2 th, f2& s2) {
     if constexpr (REREAD) asm volatile("" : "+s"(lmin4), "+s"(lmax));
-    f2 a1[2], a2[2];
+    f2 a2[2];
     // a register pair's elements broadcast by swizzle (op_sel on the pair,
     // no copy of the odd register); the first pair assigns the accumulators
-    // (d and d * d: what 0 + d and fma(d, d, 0) round to), so no zeros are
-    // materialised per sweep
+    // (d * d: what fma(d, d, 0) rounds to), so no zeros are materialised per
+    // sweep
     auto pair = [&](f2 xy, auto first) {
         const f2 d0 = xy.xx - th;
         const f2 d1 = lf_hi_minus(xy, th);
         if constexpr (decltype(first)::value) {
-            a1[0] = d0;
             a2[0] = d0 * d0;
-            a1[1] = d1;
             a2[1] = d1 * d1;
         } else {
-            a1[0] += d0;
             a2[0] = pk_fma(d0, d0, a2[0]);
-            a1[1] += d1;
             a2[1] = pk_fma(d1, d1, a2[1]);
         }
     };
@@ -228,7 +271,7 @@ MC_DEV void lf_moments(const float* xv, int len, int lmin4, int lmax, f2 th, f2&
             }
         }
     } else {
-        a1[0] = a1[1] = a2[0] = a2[1] = (f2){0.f, 0.f};
+        a2[0] = a2[1] = (f2){0.f, 0.f};
     }
     // the groups every lane holds in full (uniform), then the ragged end:
     // element e of the lanes with more elements (e < lmax, uniform bounds),
@@ -248,11 +291,9 @@ MC_DEV void lf_moments(const float* xv, int len, int lmin4, int lmax, f2 th, f2&
             if (e + k >= lmax) break;  // (uniform)
             f2 d = (f2){x[k], x[k]} - th;
             d = (e + k < len) ? d : z;
-            a1[k & 1] += d;
             a2[k & 1] = pk_fma(d, d, a2[k & 1]);
         }
     }
-    s1 = a1[0] + a1[1];
     s2 = a2[0] + a2[1];
 }
 
@@ -288,33 +329,31 @@ MC_DEV void lf_issue(const float* xv, int lmin4, LfPre& P) {
 // (by the caller, as early as it can).
 //
 // The schedule as compiled (scripts/isa_sweep.py prints it;
-// profiles/lf_sweep_pipeline/isa_result.txt): a round is 16 elements, four
-// ds_read_b128 and 48 packed instructions.  A scheduling barrier after each
-// prefetch pins the order — loads of round k + 1, the 48 instructions of
-// round k, loads of round k + 2 ... — while the compiler still counts the
-// waits (lgkmcnt) itself: the wait for a set comes a whole round after its
-// issue, and round 0's a step's fixed work after it.
+// profiles/lf_first_moment/isa_result.txt): a round is 16 elements, four
+// ds_read_b128 and 32 packed instructions (48 while the sweep summed the
+// first moment too).  A scheduling barrier after each prefetch pins the
+// order — loads of round k + 1, the 32 instructions of round k, loads of
+// round k + 2 ... — while the compiler still counts the waits (lgkmcnt)
+// itself: the wait for a set comes a whole round after its issue (33-34
+// VALU), and round 0's a step's fixed work after it.  (A third register set,
+// loads two rounds ahead, did not fit: 255 VGPRs and 96 bytes of scratch.)
 template <bool REREAD = false>
-MC_DEV void lf_moments_pre(const float* xv, int len, int lmin4, int lmax, f2 th, LfPre& P, f2& s1,
+MC_DEV void lf_moments_pre(const float* xv, int len, int lmin4, int lmax, f2 th, LfPre& P,
                            f2& s2) {
     if constexpr (REREAD) asm volatile("" : "+s"(lmin4), "+s"(lmax));
-    f2 a1[2], a2[2];
+    f2 a2[2];
     // a register pair's elements broadcast by swizzle (op_sel on the pair,
     // no copy of the odd register); the first pair assigns the accumulators
-    // (d and d * d: what 0 + d and fma(d, d, 0) round to), so no zeros are
-    // materialised per sweep
+    // (d * d: what fma(d, d, 0) rounds to), so no zeros are materialised per
+    // sweep
     auto pair = [&](f2 xy, auto first) {
         const f2 d0 = xy.xx - th;
         const f2 d1 = lf_hi_minus(xy, th);
         if constexpr (decltype(first)::value) {
-            a1[0] = d0;
             a2[0] = d0 * d0;
-            a1[1] = d1;
             a2[1] = d1 * d1;
         } else {
-            a1[0] += d0;
             a2[0] = pk_fma(d0, d0, a2[0]);
-            a1[1] += d1;
             a2[1] = pk_fma(d1, d1, a2[1]);
         }
     };
@@ -355,7 +394,7 @@ MC_DEV void lf_moments_pre(const float* xv, int len, int lmin4, int lmax, f2 th,
         }
         if (n == 1) round(B, acc);
     } else {
-        a1[0] = a1[1] = a2[0] = a2[1] = (f2){0.f, 0.f};
+        a2[0] = a2[1] = (f2){0.f, 0.f};
     }
     // the groups every lane holds in full (uniform), then the ragged end:
     // element e of the lanes with more elements (e < lmax, uniform bounds),
@@ -375,11 +414,9 @@ MC_DEV void lf_moments_pre(const float* xv, int len, int lmin4, int lmax, f2 th,
             if (e + k >= lmax) break;  // (uniform)
             f2 d = (f2){x[k], x[k]} - th;
             d = (e + k < len) ? d : z;
-            a1[k & 1] += d;
             a2[k & 1] = pk_fma(d, d, a2[k & 1]);
         }
     }
-    s1 = a1[0] + a1[1];
     s2 = a2[0] + a2[1];
 }
 
@@ -614,6 +651,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
     const float* xv[RS];
     int len[RS], lmin4[RS], lmax[RS];
     f2 cnt[RS];
+    float mc_c[RS], mc_R[RS];  // the run's centre and centred sum (lf_run_consts), pinned
     bool pdir[RS];
 #pragma unroll
     for (int r = 0; r < RS; ++r) {
@@ -627,6 +665,11 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             xv[r] = sd + tt[0].doff[0] + tt[0].toff[r] + 4 * j;
         }
         cnt[r] = bc2((float)len[r]);
+        {
+            const f2 cr = lf_run_consts(xv[r], len[r]);
+            mc_c[r] = vpin(cr[0]);
+            mc_R[r] = vpin(cr[1]);
+        }
         // the slot's longest run (uniform: a wave max, once per launch)
         {
             int m = len[r];
@@ -649,9 +692,11 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
              d_clogs = vpin(bc2(F.d_clogs));
     const f2 half = bc2(0.5f), one = bc2(1.0f);
     const float lp_const = vpin(P.lp_const);
-    // the swept terms' moment sums at the current point, both chains (a lane
-    // without elements never writes its sums: they stay the zeros they are
-    // declared with, so no zeros are materialised per sweep)
+    // the swept terms' second-moment sums at the current point, both chains (a
+    // lane without elements never writes its sums: they stay the zeros they
+    // are declared with, so no zeros are materialised per sweep); the first
+    // moment is formed from the position and the run's constants where the
+    // step finishes the term (lf_m1)
     // PRE — one slot, a compile-time form and one lane per parameter compiled
     // in (LFS_REP1: whole runs, several rounds a sweep; the Large shape): the
     // step issues the sweep's first loads itself (sweep_issue, ahead of the
@@ -666,15 +711,14 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
     auto sweep_issue = [&](LfPre& pre) {
         if constexpr (PRE) lf_issue<true>(xv[0], lmin4[0], pre);
     };
-    auto sweep = [&](f2 (&s1)[RS], f2 (&s2)[RS], LfPre& pre) {
+    auto sweep = [&](f2 (&s2)[RS], LfPre& pre) {
 #pragma unroll
         for (int r = 0; r < RS; ++r) {
             if (len[r] > 0) {
                 if constexpr (PRE)
-                    lf_moments_pre<true>(xv[r], len[r], lmin4[r], lmax[r], q[r], pre, s1[r],
-                                         s2[r]);
+                    lf_moments_pre<true>(xv[r], len[r], lmin4[r], lmax[r], q[r], pre, s2[r]);
                 else
-                    lf_moments<RS == 1>(xv[r], len[r], lmin4[r], lmax[r], q[r], s1[r], s2[r]);
+                    lf_moments<RS == 1>(xv[r], len[r], lmin4[r], lmax[r], q[r], s2[r]);
             }
         }
     };
@@ -916,14 +960,14 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             sh.iv = sh.is * sh.is;
             gown = vpin(own_grad(sh.v));  // for the step at this position
         };
-        f2 M1[RS], M2[RS];
+        f2 M2[RS];
 #pragma unroll
-        for (int r = 0; r < RS; ++r) M1[r] = M2[r] = (f2){0.f, 0.f};
+        for (int r = 0; r < RS; ++r) M2[r] = (f2){0.f, 0.f};
         LfPre pre;
         sweep_issue(pre);
         drift_private(false);
         drift_shared(false);
-        sweep(M1, M2, pre);
+        sweep(M2, pre);
         if (xchk && it == cfg.iter_begin) {  // (before the launch's first publish)
             const bool same = xcd_agree(xpoll, xslots, S, ebase + 1, ok);
             // (diagnostic: blocks found on one XCD / not, counted by slice 0,
@@ -991,15 +1035,21 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                 for (int r = 0; r < RS; ++r) {
                     const bool on = len[r] != 0;
                     const f2 z = {0.f, 0.f};
+                    // the first moment at q[r], where the sweep ran (the
+                    // drift to the next position follows this finish): the
+                    // data's share is the run's constants; an empty lane's
+                    // stays the zero the skipped sweep left
+                    const f2 m1 = lf_m1(cnt[r], mc_c[r], mc_R[r], q[r]);
+                    const f2 M1r = on ? m1 : z;
                     if (RS == 1) {
                         // one slot: an empty lane's moment sums and count are
                         // zeros (the sweep skips it), so are its gradient and
                         // cotangent; its log p is selected away
-                        g[r] = sw_w * (M1[r] * iv);
+                        g[r] = sw_w * (M1r * iv);
                         cs = sw_w * ((M2[r] * iv - cnt[r]) * is);
                         cs0 = g0r[r] = false;
                     } else if (on) {
-                        acc(g[r], g0r[r], sw_w * (M1[r] * iv));
+                        acc(g[r], g0r[r], sw_w * (M1r * iv));
                         acc(cs, cs0, sw_w * ((M2[r] * iv - cnt[r]) * is));
                     }
                     if (lst) {
@@ -1193,7 +1243,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             // A/B 83.2 vs 94.7 M steps/s, profiles/r4/ab)
             if constexpr (!LAST) {
                 drift_private(true);
-                sweep(M1, M2, pre);
+                sweep(M2, pre);
             }
             // the last step: the next iteration's draws, while the records travel
             if constexpr (LAST) ahead();
