@@ -25,6 +25,9 @@
  *   examples/06_nuts_comparison.py:22-41 compute_ess   mc_series_stats (MC_ST_ESS)
  *   README.md:214 roadmap "R-hat" (no reference code)  mc_stats_reduce + mc_rhat
  *   mlx_mcmc/inference/mcmc.py:191-227 summary         mc_pool_moments, mc_select
+ *   README.md roadmap "Model comparison (WAIC, LOO)"   mc_pointwise_stats (no reference code)
+ *   README.md:216 roadmap "Posterior predictive checks" mc_predictive, mc_predictive_draw
+ *     (no reference code; Distribution.sample stays the host sampler)
  *
  * The reference is pure Python on MLX and has no FFI of its own; the
  * Python host layer of this repository (mlx_mcmc_amd/_lib.py) binds these
@@ -637,6 +640,7 @@ int mc_mh_run(const mc_program* prog, const mc_run_config* cfg, double proposal_
 #define MC_RNG_TAG_DEPTH    4
 #define MC_RNG_TAG_MERGE    5
 #define MC_RNG_TAG_PROPOSAL 6   /* Metropolis-Hastings random-walk noise      */
+#define MC_RNG_TAG_PREDICT  7   /* posterior predictive replicates (mc_predictive) */
 #define MC_RNG_TAG_USER     16
 int mc_rng_fill(uint64_t seed, uint32_t chain, uint32_t iteration,
                 uint32_t tag, uint32_t sub, uint32_t index0, int64_t n,
@@ -733,6 +737,70 @@ int64_t mc_pointwise_workspace_bytes(const mc_program* prog, int64_t C, int64_t 
 int mc_pointwise_stats(const mc_program* prog, int64_t C, int64_t S,
                        const float* samples_dev, double* stats_dev, float* matrix_dev,
                        void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
+/* ---- posterior predictive replicates over kept draws (no reference code: its
+ * README roadmap lists posterior predictive checks) --------------------------
+ * On the pointwise view of a likelihood program (mc_program_enable_pointwise,
+ * reused as built): every element of every term is one observation o, in the
+ * caller's order.  A replicate y_rep[c, s, o] is a pure function of (seed,
+ * global chain c + chain_offset, iteration s + iter_offset, o) and the term's
+ * f32 operand values at that draw (what the pointwise kernel forms; the affine
+ * loc as m + b * x) — not of the block split, of how chains are split over
+ * calls or ranks, of thin, or of whether replicates are stored.  The term's
+ * weight is ignored: a replicate comes from the untempered observation model.
+ *
+ * Counter: Philox (chain, iteration, MC_RNG_TAG_PREDICT << 24 | sub, o), words
+ * w.x .. w.w; sub is the attempt of a rejection sampler, 0 elsewhere; Beta's
+ * second Gamma uses sub = 0x100 + attempt.  With z0 the first normal of
+ * Box-Muller on (w.x, w.y), u01(w) = (f32(w) + 0.5) 2^-32 and log the
+ * samplers' f32 log (csrc/philox.h mc_box_muller, mc_u01_boxf, mc_logf_unit;
+ * IEEE operations only: host and device give the same bits):
+ *   Normal       loc + scale * z0
+ *   HalfNormal   |scale * z0|
+ *   Exponential  -log(u01(w.x)) / rate
+ *   Gamma(a, b)  Marsaglia and Tsang (2000): d = a' - 1/3, c = 1 / sqrt(9 d),
+ *                per attempt x = z0, v = (1 + c x)^3, accepted when v > 0 and
+ *                log u01(w.z) < x^2 / 2 + d (1 - v + log v); the variate is
+ *                d v / b.  a < 1: a' = a + 1 and the variate is multiplied by
+ *                U^(1/a) = f32(exp(f64(log U / a))), U = u01 of attempt 0's
+ *                w.w (the one value where host and device may differ, in the
+ *                last bit, with probability ~1e-8); else a' = a.  At most 32
+ *                attempts (each rejects with probability < 0.05), then NaN.
+ *   Beta(a, b)   X / (X + Y), X ~ Gamma(a, 1), Y ~ Gamma(b, 1)
+ * A scale, rate or shape that is <= 0 or NaN gives NaN (as a NaN loc does),
+ * never a hang.  Expression and identity terms have no sampling distribution:
+ * MC_ERR_UNSUPPORTED, naming the term, before any launch.
+ *
+ * mc_predictive_draw: the scalar definition on the host (no device, no
+ * allocation): *out = the replicate of observation obs under (dist, loc or
+ * alpha, scale / rate / beta).  MC_ERR_UNSUPPORTED for any other dist.
+ *
+ * mc_predictive: samples_dev is the [C, S, D] buffer; thin >= 1 processes
+ * iterations s = 0, thin, 2 thin, ... of every chain (S' = ceil(S / thin); the
+ * counter carries the true s + iter_offset).  stats_dev[f * M + o] (f64)
+ * receives the fields below over the C * S' processed draws; yrep_dev is NULL
+ * or [C, S', M] f32 and then receives every replicate.  A launch function:
+ * asynchronous, no allocation, no synchronisation; workspace_dev holds
+ * mc_predictive_workspace_bytes(prog, C, S, thin) bytes (0 is possible).  The
+ * block split depends on (C, S, thin, the program) only and the partials are
+ * merged in block order: two calls give the same bits, with or without
+ * yrep_dev.  The five fields are a mergeable partial (Chan's update over the
+ * finite counts N - NONFINITE, counts added).                               */
+#define MC_PP_N         0   /* draws processed                                */
+#define MC_PP_MEAN      1   /* mean of the finite replicates (NaN: none)      */
+#define MC_PP_M2        2   /* their sum of squared deviations from the mean  */
+#define MC_PP_BELOW     3   /* finite replicates < the observation (the term's
+                               value operand at that draw)                    */
+#define MC_PP_NONFINITE 4   /* replicates that are +-inf or NaN               */
+#define MC_PP_COUNT     5
+int mc_predictive_draw(int dist, float loc_or_alpha, float scale_or_rate_or_beta,
+                       uint64_t seed, uint32_t chain, uint32_t iter, uint32_t obs, float* out);
+int64_t mc_predictive_workspace_bytes(const mc_program* prog, int64_t C, int64_t S,
+                                      int64_t thin);
+int mc_predictive(const mc_program* prog, int64_t C, int64_t S, int64_t thin, uint64_t seed,
+                  int64_t chain_offset, int64_t iter_offset, const float* samples_dev,
+                  double* stats_dev, float* yrep_dev, void* workspace_dev,
+                  int64_t workspace_bytes, void* hip_stream);
 
 const char* mc_last_error(void);
 int32_t mc_abi_version(void);

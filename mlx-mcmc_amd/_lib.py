@@ -56,6 +56,10 @@ MC_ST_COUNT = 7
 MC_PW_MAX, MC_PW_SUMEXP, MC_PW_N, MC_PW_MEAN, MC_PW_M2, MC_PW_NONFINITE = range(6)
 MC_PW_COUNT = 6
 
+# mc_predictive fields (include/mcmc355.h)
+MC_PP_N, MC_PP_MEAN, MC_PP_M2, MC_PP_BELOW, MC_PP_NONFINITE = range(5)
+MC_PP_COUNT = 5
+
 MC_OP_NONE = 0
 MC_OP_CONST = 1
 MC_OP_PSCALAR = 2
@@ -73,6 +77,7 @@ MC_RNG_TAG_SLICE = 3
 MC_RNG_TAG_DEPTH = 4
 MC_RNG_TAG_MERGE = 5
 MC_RNG_TAG_PROPOSAL = 6
+MC_RNG_TAG_PREDICT = 7
 MC_RNG_TAG_USER = 16
 
 
@@ -296,6 +301,14 @@ SIGNATURES = [
     ("mc_pointwise_workspace_bytes", ctypes.c_int64, [_VP, ctypes.c_int64, ctypes.c_int64]),
     ("mc_pointwise_stats", ctypes.c_int,
      [_VP, ctypes.c_int64, ctypes.c_int64, _VP, _VP, _VP, _VP, ctypes.c_int64, _VP]),
+    ("mc_predictive_draw", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32,
+      ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float)]),
+    ("mc_predictive_workspace_bytes", ctypes.c_int64,
+     [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    ("mc_predictive", ctypes.c_int,
+     [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64,
+      ctypes.c_int64, _VP, _VP, _VP, _VP, ctypes.c_int64, _VP]),
     ("mc_last_error", ctypes.c_char_p, []),
     ("mc_abi_version", ctypes.c_int32, []),
 ]

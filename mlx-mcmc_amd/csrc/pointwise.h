@@ -338,8 +338,10 @@ __global__ __launch_bounds__(kPwBlock) void k_pointwise(PwCtx P, int64_t N, int6
 }
 
 // stats[f * M + o] from the B partials of observation o, in block order
-__global__ __launch_bounds__(256) void k_pw_merge(const double* __restrict__ part, int64_t M,
-                                                  int32_t B, double* __restrict__ stats) {
+// (internal linkage: predictive.h brings this header into a second unit)
+static __global__ __launch_bounds__(256) void k_pw_merge(const double* __restrict__ part,
+                                                         int64_t M, int32_t B,
+                                                         double* __restrict__ stats) {
     const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= M) return;
     auto load = [&](int b) {

@@ -3,21 +3,9 @@
 // mc_pointwise_workspace_bytes, mc_pointwise_stats).
 #include "host.h"
 #include "pointwise.h"
+#include "pw_view.h"
 
 namespace {
-
-// Device tables of the pointwise view (mc_program::pw).
-struct PwView {
-    DevTerm* d_terms = nullptr;
-    DevExprNode* d_nodes = nullptr;
-    float* d_data = nullptr;
-    int32_t* d_index = nullptr;
-    PwTile* d_tiles = nullptr;
-    int32_t ntiles = 0;
-    int64_t M = 0;
-    int32_t max_nodes = 0;  // largest expression term (0: fused terms only)
-    bool lg = false;        // a Gamma / Beta term whose normaliser follows the draw
-};
 
 template <typename T>
 hipError_t pw_upload(T** dst, const T* src, size_t n) {
@@ -31,22 +19,6 @@ int64_t pw_elements(const mc_program* p) {
     int64_t m = 0;
     for (const DevTerm& t : p->pw_terms) m += t.n;
     return m;
-}
-
-// Draw blocks B and draws per block for N = C * S draws over `ntiles` tiles:
-// enough workgroups to fill the device whatever it is (a constant target, not
-// a query), at least 32 draws per block so that a partial's 48 bytes per
-// observation stay small beside the block's work.  A function of (N, ntiles)
-// only; every block holds at least one draw.
-constexpr int64_t kPwTargetGroups = 4096;
-constexpr int64_t kPwMinDraws = 32;
-constexpr int64_t kPwMaxB = 1024;
-void pw_split(int64_t N, int64_t ntiles, int64_t* B, int64_t* per) {
-    int64_t b = (kPwTargetGroups + ntiles - 1) / std::max<int64_t>(1, ntiles);
-    b = std::min(b, std::max<int64_t>(1, N / kPwMinDraws));
-    b = std::max<int64_t>(1, std::min(b, kPwMaxB));
-    *per = (N + b - 1) / b;
-    *B = (N + *per - 1) / *per;
 }
 
 }  // namespace
@@ -152,15 +124,7 @@ extern "C" int mc_pointwise_stats(const mc_program* p, int64_t C, int64_t S, con
         return fail(MC_ERR_INVALID, "pointwise: the workspace needs %lld bytes",
                     (long long)need);
     hipStream_t st = (hipStream_t)hip_stream;
-    PwCtx X;
-    X.terms = v->d_terms;
-    X.nodes = v->d_nodes;
-    X.data = v->d_data;
-    X.index = v->d_index;
-    X.tiles = v->d_tiles;
-    X.M = v->M;
-    X.D = p->D;
-    X.ntiles = v->ntiles;
+    const PwCtx X = pw_ctx_of(p, v);
     // one block of draws: its partial is the result
     double* part = B > 1 ? (double*)ws : stats;
     const dim3 grid((unsigned)v->ntiles, (unsigned)B);

@@ -24,11 +24,19 @@ values) or a handful of order statistics come back to the host.
   WAIC from them (Vehtari, Gelman and Gabry 2017); ``merge_pointwise`` is the
   host statement of the merge the device and the ranks apply.  Out of scope:
   PSIS-LOO (a per-observation tail fit over draws; ``matrix=True`` hands small
-  problems to other tools), posterior predictive sampling, and the expression
-  JIT for likelihoods (expression terms run the node interpreter).
+  problems to other tools) and the expression JIT for likelihoods (expression
+  terms run the node interpreter).
+* ``posterior_predictive(log_likelihood, samples, layout)`` — for every
+  observation of the same kind of likelihood, one replicate per kept draw from
+  the term's own distribution at that draw (mc_predictive, csrc/predictive.h),
+  reduced on the device to mergeable statistics: predictive mean and variance,
+  and the fraction of replicates below the observation (a PIT value).  The
+  C x S x M replicates are stored only on request.  ``merge_predictive`` is
+  the host statement of the merge.
 
 No CPU fallback: without the library these raise ``EngineUnavailable``
-(``merge_pointwise`` and ``waic_from_stats`` are pure host arithmetic).
+(``merge_pointwise``, ``merge_predictive`` and ``waic_from_stats`` are pure
+host arithmetic).
 """
 from __future__ import annotations
 
@@ -431,3 +439,102 @@ def waic(log_likelihood_fn, samples, layout=None, *, group=None) -> dict:
     support: reported, never raised)."""
     return waic_from_stats(pointwise_log_likelihood(log_likelihood_fn, samples, layout,
                                                     group=group))
+
+
+# ------------------------------------------------- posterior predictive -----
+PP_FIELDS = ("n", "mean", "m2", "below", "nonfinite")
+
+
+def merge_predictive(parts):
+    """Merge posterior predictive partials (dicts of the five [M] float64
+    arrays ``n``, ``mean``, ``m2``, ``below``, ``nonfinite`` of
+    ``posterior_predictive``, each over its own shard of draws) in order.
+
+    ``mean`` and ``m2`` are moments of the finite replicates: Chan's update
+    over the finite counts ``n - nonfinite`` (a side without finite replicates
+    leaves the other's moments; both without: NaN), the three counts added.
+    The device merge (csrc/predictive.h k_pp_merge) and the rank merge apply
+    the same rules."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_predictive needs at least one partial")
+    acc = {f: np.array(parts[0][f], dtype=np.float64, copy=True) for f in PP_FIELDS}
+    with np.errstate(all="ignore"):
+        for p in parts[1:]:
+            b = {f: np.asarray(p[f], np.float64) for f in PP_FIELDS}
+            na, nb = acc["n"] - acc["nonfinite"], b["n"] - b["nonfinite"]
+            d = b["mean"] - acc["mean"]
+            r = 1.0 / (na + nb)
+            mean = acc["mean"] + d * (nb * r)
+            m2 = acc["m2"] + (b["m2"] + d * d * (na * nb * r))
+            keep, take = nb == 0, na == 0
+            acc = {"n": acc["n"] + b["n"],
+                   "mean": np.where(keep, acc["mean"], np.where(take, b["mean"], mean)),
+                   "m2": np.where(keep, acc["m2"], np.where(take, b["m2"], m2)),
+                   "below": acc["below"] + b["below"],
+                   "nonfinite": acc["nonfinite"] + b["nonfinite"]}
+    return acc
+
+
+def posterior_predictive(log_likelihood_fn, samples, layout=None, *, seed=0, thin=1,
+                         replicates=False, chain_offset=0, iter_offset=0, group=None):
+    """Posterior predictive replicates and per-observation checks over the
+    kept draws, on the device.
+
+    ``log_likelihood_fn`` and ``samples`` / ``layout`` are those of
+    ``pointwise_log_likelihood``: every element of every term of the traced
+    likelihood is one observation.  For every processed draw (iterations 0,
+    ``thin``, 2 ``thin``, ... of every chain: S' = ceil(S / thin)) and
+    observation, one replicate is drawn from the term's distribution — Normal,
+    HalfNormal, Exponential, Gamma or Beta — with the operand values of that
+    draw.  A replicate is a pure function of (``seed``, chain index +
+    ``chain_offset``, iteration index + ``iter_offset``, observation) and those
+    operand values (include/mcmc355.h), so shards of chains or iterations and
+    thinned runs reproduce the rows of the whole.  A term's weight (``mx.mean``,
+    a tempering factor) is ignored: replicates come from the untempered
+    observation model.  Expression and identity terms have no sampling
+    distribution: ``EngineError`` (MC_ERR_UNSUPPORTED) before any launch.
+
+    Returns float64 NumPy [M] arrays ``n`` (draws processed), ``mean`` and
+    ``m2`` (moments of the finite replicates), ``below`` (finite replicates
+    below the observation, the term's value at that draw), ``nonfinite``
+    (replicates of a draw with an invalid scale, rate or shape: NaN, counted,
+    never raised) — a partial ``merge_predictive`` combines with other shards —
+    and the derived ``var`` = m2 / (n_finite - 1) and ``pit`` = below /
+    n_finite, n_finite = n - nonfinite.  ``replicates=True`` adds
+    ``replicates``, the [C, S', M] float32 device tensor (small problems only).
+    With an initialised process group (``group=False`` stays local) the ranks'
+    partials are gathered and merged in rank order; the replicates stay this
+    rank's."""
+    import torch
+
+    from . import _trace
+
+    thin = int(thin)
+    if thin < 1:
+        raise ValueError("thin must be >= 1")
+    x, lay = _pointwise_inputs(samples, layout)
+    C, S, D = x.shape
+    prog = _trace.pointwise_program(log_likelihood_fn, lay)
+    lib = _lib.load()
+    M = prog.num_elements
+    nb = lib.mc_predictive_workspace_bytes(prog.handle, C, S, thin)
+    if nb < 0:   # (an unsupported term is reported here: nothing is launched)
+        _lib.check(int(nb))
+    Sp = (S + thin - 1) // thin
+    st = torch.empty((_lib.MC_PP_COUNT, M), dtype=torch.float64, device=x.device)
+    rep = torch.empty((C, Sp, M), dtype=torch.float32, device=x.device) if replicates else None
+    ws = torch.empty(max(int(nb), 1), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.mc_predictive(prog.handle, C, S, thin, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                 int(chain_offset), int(iter_offset), _lib.ptr(x), _lib.ptr(st),
+                                 _lib.ptr(rep), _lib.ptr(ws), nb, _lib.stream_handle()))
+    host = st.cpu().numpy()   # (synchronises: prog, x and ws outlive the launch)
+    part = {f: host[k].copy() for k, f in enumerate(PP_FIELDS)}
+    out = merge_predictive(_gather_parts(part, group))
+    with np.errstate(all="ignore"):
+        nfin = out["n"] - out["nonfinite"]
+        out["var"] = out["m2"] / (nfin - 1.0)
+        out["pit"] = out["below"] / nfin
+    if replicates:
+        out["replicates"] = rep
+    return out

@@ -35,9 +35,13 @@ class MCMC:
         self.samples = None
         self.acceptance_rate = None
         self.info = None
+        self._random_seed = 0
+        self._chain_offset = 0
 
     def run(self, initial_params, num_samples=1000, num_warmup=1000, method='metropolis',
             proposal_scale=0.1, random_seed=0, verbose=True, **kwargs):
+        self._random_seed = random_seed
+        self._chain_offset = int(kwargs.get('chain_offset', 0))
         if method in ('hmc', 'nuts'):
             if verbose:
                 print(f"\n{'=' * 70}")
@@ -155,6 +159,18 @@ class MCMC:
         """WAIC of ``log_likelihood_fn`` over the kept draws (diagnostics.waic)."""
         samples, layout = self._kept_draws()
         return _diag.waic(log_likelihood_fn, samples, layout, group=False)
+
+    def posterior_predictive(self, log_likelihood_fn, seed=None, thin=1, replicates=False):
+        """Posterior predictive replicates of ``log_likelihood_fn``'s observations
+        over the kept draws, reduced on the device to per-observation mean,
+        variance and PIT (diagnostics.posterior_predictive).  ``seed`` defaults
+        to the run's ``random_seed``; chains are numbered from the run's
+        ``chain_offset``."""
+        samples, layout = self._kept_draws()
+        return _diag.posterior_predictive(
+            log_likelihood_fn, samples, layout,
+            seed=self._random_seed if seed is None else seed, thin=thin, replicates=replicates,
+            chain_offset=self._chain_offset, group=False)
 
     def print_summary(self, credible_interval=0.95):
         summary = self.summary(credible_interval)
