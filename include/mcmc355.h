@@ -27,6 +27,7 @@
  *   mlx_mcmc/inference/mcmc.py:191-227 summary         mc_pool_moments, mc_select
  *   README.md roadmap "Model comparison (WAIC, LOO)"   mc_pointwise_stats (no reference code)
  *   README.md:216 roadmap "Posterior predictive checks" mc_predictive, mc_predictive_draw
+ *   README.md roadmap "Model comparison (WAIC, LOO)"   mc_psis_loo, mc_psis_fit_host (no reference code)
  *     (no reference code; Distribution.sample stays the host sampler)
  *
  * The reference is pure Python on MLX and has no FFI of its own; the
@@ -801,6 +802,76 @@ int mc_predictive(const mc_program* prog, int64_t C, int64_t S, int64_t thin, ui
                   int64_t chain_offset, int64_t iter_offset, const float* samples_dev,
                   double* stats_dev, float* yrep_dev, void* workspace_dev,
                   int64_t workspace_bytes, void* hip_stream);
+
+/* ---- PSIS-LOO over kept draws (no reference code: its README roadmap lists
+ * "Model comparison (WAIC, LOO)") ---------------------------------------------
+ * Pareto-smoothed importance sampling leave-one-out (Vehtari, Gelman and Gabry
+ * 2017) on the pointwise view of a likelihood program
+ * (mc_program_enable_pointwise, reused as built).  For observation o over the
+ * N = C * S draws, l_s is the f32 pointwise value mc_pointwise_stats forms (the
+ * same bits; -0 taken as +0); everything after the selection is f64:
+ *   1 tail length  Mt = min(ceil(min(N / 5, 3 sqrt(N / r_eff))), N - 1), r_eff a
+ *                  positive scalar (mc_psis_tail_len)
+ *   2 cutoff       L, the (Mt + 1)-th smallest l counted with multiplicity
+ *   3 tail         { s : l_s < L } (strict: ties at the cutoff drop out, so
+ *                  n = |tail| <= Mt); lmin the smallest l
+ *   4 exceedances  the tail in decreasing l, t_1 >= ... >= t_n;
+ *                  e_c = exp(lmin - L), y_j = exp(lmin - t_j) - e_c (ascending)
+ *   5 fit          Zhang and Stephens (2009) with the PSIS paper's prior.
+ *                  n <= 4: khat = +inf, sigma = NaN, nothing is smoothed.  Else
+ *                  m = 30 + floor(sqrt(n)); y_q the floor(n / 4 + 1/2)-th
+ *                  smallest y; b_i = (1 - sqrt(m / (i - 1/2))) / (3 y_q) + 1 / y_n
+ *                  (i = 1 .. m); kappa_i = mean_j log1p(-b_i y_j);
+ *                  L_i = n (log(-b_i / kappa_i) - kappa_i - 1);
+ *                  w_i = 1 / sum_j exp(L_j - L_i), normalised to sum 1 (no
+ *                  small-weight filter); bbar = sum w_i b_i;
+ *                  kbar = mean_j log1p(-bbar y_j); sigma = -kbar / bbar;
+ *                  khat = (n kbar + 5) / (n + 10).  IEEE arithmetic throughout:
+ *                  a degenerate tail gives NaN khat and sigma, never an error.
+ *   6 smoothing    when khat is finite and sigma > 0: p_j = (j - 1/2) / n,
+ *                  q_j = sigma expm1(-khat log1p(-p_j)) / khat (|khat| <
+ *                  DBL_EPSILON: -sigma log1p(-p_j)); the tail's log weights
+ *                  become lw_j = min(log(q_j + e_c), 0) in rank order.  Every
+ *                  other draw, and the tail when nothing is smoothed, keeps
+ *                  lw_s = lmin - l_s.
+ *   7 elpd         log((N - n) + sum_tail exp(t_j + lw_j - lmin))
+ *                  - log(sum_tail exp(lw_j) + sum_rest exp(lmin - l_s)) + lmin
+ *                  (the difference of the logs first); the rest sum is an f64
+ *                  sum per block of draws, the blocks merged in order.
+ *   8 non-finite   an observation with any non-finite draw gets NaN ELPD, KHAT
+ *                  and SIGMA: counted by the caller (MC_PW_NONFINITE), never
+ *                  raised.
+ *
+ * mc_psis_fit_host: steps 5 and 6 on the host (no device), the code the fit
+ * kernel runs: tail_desc[n] is the tail in decreasing l; *khat and *sigma are
+ * written; lw_out is NULL or [n] and receives the log weights in rank order.
+ *
+ * mc_psis_loo: a launch function (asynchronous, no allocation, no
+ * synchronisation).  out_dev[f * M + o] (f64) receives the fields below;
+ * tail_dev is NULL or [M, Mt] f32 and receives each observation's tail in
+ * ascending l, NaN after its n-th entry.  workspace_dev holds
+ * mc_psis_workspace_bytes(prog, C, S, r_eff) bytes: O(M * Mt) f32 for the tails
+ * plus the per-block partials; the C * S * M matrix is never stored (the draws
+ * are re-evaluated: eight passes of an exact radix select of L, one gather).
+ * Mt above 2048 (kPsisMaxTail: the fit kernel sorts a tail in LDS) is
+ * MC_ERR_UNSUPPORTED from mc_psis_workspace_bytes, before any launch.  The
+ * split into blocks depends on (C, S, r_eff, the program) only; counts are
+ * integers and every f64 sum has a fixed order: two calls give the same bits,
+ * with or without tail_dev.  No atomics, nothing waits on another workgroup. */
+#define MC_PSIS_ELPD    0   /* elpd_loo of the observation                     */
+#define MC_PSIS_KHAT    1   /* Pareto shape estimate (+inf: n <= 4)            */
+#define MC_PSIS_SIGMA   2   /* Pareto scale estimate (NaN: n <= 4)             */
+#define MC_PSIS_CUTOFF  3   /* L                                               */
+#define MC_PSIS_MIN     4   /* lmin                                            */
+#define MC_PSIS_TAILN   5   /* n                                               */
+#define MC_PSIS_COUNT   6
+int64_t mc_psis_tail_len(int64_t N, double r_eff);
+int mc_psis_fit_host(const float* tail_desc, int64_t n, float cutoff, float lmin,
+                     double* khat, double* sigma, double* lw_out);
+int64_t mc_psis_workspace_bytes(const mc_program* prog, int64_t C, int64_t S, double r_eff);
+int mc_psis_loo(const mc_program* prog, int64_t C, int64_t S, double r_eff,
+                const float* samples_dev, double* out_dev, float* tail_dev,
+                void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
 const char* mc_last_error(void);
 int32_t mc_abi_version(void);

@@ -60,6 +60,11 @@ MC_PW_COUNT = 6
 MC_PP_N, MC_PP_MEAN, MC_PP_M2, MC_PP_BELOW, MC_PP_NONFINITE = range(5)
 MC_PP_COUNT = 5
 
+# mc_psis_loo fields (include/mcmc355.h)
+(MC_PSIS_ELPD, MC_PSIS_KHAT, MC_PSIS_SIGMA, MC_PSIS_CUTOFF, MC_PSIS_MIN,
+ MC_PSIS_TAILN) = range(6)
+MC_PSIS_COUNT = 6
+
 MC_OP_NONE = 0
 MC_OP_CONST = 1
 MC_OP_PSCALAR = 2
@@ -309,6 +314,15 @@ SIGNATURES = [
     ("mc_predictive", ctypes.c_int,
      [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64,
       ctypes.c_int64, _VP, _VP, _VP, _VP, ctypes.c_int64, _VP]),
+    ("mc_psis_tail_len", ctypes.c_int64, [ctypes.c_int64, ctypes.c_double]),
+    ("mc_psis_fit_host", ctypes.c_int,
+     [_VP, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_double),
+      ctypes.POINTER(ctypes.c_double), _VP]),
+    ("mc_psis_workspace_bytes", ctypes.c_int64,
+     [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_double]),
+    ("mc_psis_loo", ctypes.c_int,
+     [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _VP, _VP, _VP, _VP, ctypes.c_int64,
+      _VP]),
     ("mc_last_error", ctypes.c_char_p, []),
     ("mc_abi_version", ctypes.c_int32, []),
 ]

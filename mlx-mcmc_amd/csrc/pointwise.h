@@ -240,6 +240,61 @@ MC_DEV float pw_expr(const DevTerm& T, const PwCtx& P, const float* __restrict__
     return T.weight * val[nn - 1];
 }
 
+// The thread's element of term T, decoded once: its operands (at most five)
+// and eval_term's ulogs / ulg choices.
+struct PwElem {
+    PwOp ov, om, os, ob, ox;
+    bool expr, aff, clogs, need_logs, need_lg, use_clg;
+};
+template <int NMAX>
+MC_DEV PwElem pw_elem(const DevTerm& T, const PwCtx& P, int64_t i) {
+    PwElem E;
+    E.expr = false;
+    if constexpr (NMAX > 0) E.expr = T.dist == MC_DIST_EXPR;
+    E.aff = E.clogs = E.need_logs = E.need_lg = E.use_clg = false;
+    E.ov = E.om = E.os = E.ob = E.ox = PwOp{0, 0.0f, 0, false};
+    if (!E.expr) {
+        E.ov = pw_operand(T.op[0], i, P);
+        E.om = pw_operand(T.op[1], i, P);
+        E.os = pw_operand(T.op[2], i, P);
+        E.aff = T.affine != 0;
+        if (E.aff) {
+            E.ob = pw_operand(T.ab, i, P);
+            E.ox = pw_operand(T.ax, i, P);
+        }
+        // eval_term's ulogs / ulg: the precomputed f32 log of a constant scale
+        // and normaliser of constant shapes, else from the current values
+        E.clogs = T.op[2].kind == MC_OP_CONST;
+        E.need_logs = T.dist == MC_DIST_NORMAL || T.dist == MC_DIST_HALFNORMAL ||
+                      T.dist == MC_DIST_EXPONENTIAL || T.dist == MC_DIST_GAMMA;
+        E.need_lg = T.dist == MC_DIST_GAMMA || T.dist == MC_DIST_BETA;
+        E.use_clg = !lg_per_element(T.dist, T.op[1].kind, T.op[2].kind) &&
+                    !(T.op[1].kind == MC_OP_PSCALAR || T.op[2].kind == MC_OP_PSCALAR);
+    }
+    return E;
+}
+
+// The pointwise value of the element under the draw whose row is q: the one
+// definition every unit on the pointwise view evaluates (k_pointwise, psis.h),
+// so they form the same bits.
+template <int NMAX, bool LG>
+MC_DEV float pw_elem_value(const PwElem& E, const DevTerm& T, const PwCtx& P,
+                           const float* __restrict__ q, int64_t i) {
+    if constexpr (NMAX > 0) {
+        if (E.expr) return pw_expr<NMAX>(T, P, q, i);
+    }
+    const float v = pw_value(E.ov, q);
+    float m = pw_value(E.om, q);
+    if (E.aff) m = m + pw_value(E.ob, q) * pw_value(E.ox, q);
+    const float s = pw_value(E.os, q);
+    const float logs = E.need_logs ? (E.clogs ? T.clogs : logf(s)) : 0.0f;
+    float lg = T.clg;
+    if constexpr (LG) {
+        if (E.need_lg && !E.use_clg) lg = lg_norm_dev(T.dist, m, s);
+    }
+    return T.weight * elem_eval(T.dist, T.c0, v, m, s, logs, lg).lp;
+}
+
 // NMAX == 0: fused terms only; 16 / 32: expression terms of up to that many
 // nodes as well (separate instantiations, as the tape kernels' EX variants:
 // programs without expression terms keep the fused path's registers).
@@ -262,29 +317,7 @@ __global__ __launch_bounds__(kPwBlock) void k_pointwise(PwCtx P, int64_t N, int6
 
     PwAcc A = {-(double)__builtin_inff(), 0.0, 0.0, 0.0, 0.0, 0.0};
     double nfsum = 0.0;
-    bool expr = false;
-    if constexpr (NMAX > 0) expr = T.dist == MC_DIST_EXPR;
-
-    PwOp ov, om, os, ob, ox;
-    bool aff = false, clogs = false, need_logs = false, need_lg = false, use_clg = false;
-    if (!expr) {
-        ov = pw_operand(T.op[0], i, P);
-        om = pw_operand(T.op[1], i, P);
-        os = pw_operand(T.op[2], i, P);
-        aff = T.affine != 0;
-        if (aff) {
-            ob = pw_operand(T.ab, i, P);
-            ox = pw_operand(T.ax, i, P);
-        }
-        // eval_term's ulogs / ulg: the precomputed f32 log of a constant scale
-        // and normaliser of constant shapes, else from the current values
-        clogs = T.op[2].kind == MC_OP_CONST;
-        need_logs = T.dist == MC_DIST_NORMAL || T.dist == MC_DIST_HALFNORMAL ||
-                    T.dist == MC_DIST_EXPONENTIAL || T.dist == MC_DIST_GAMMA;
-        need_lg = T.dist == MC_DIST_GAMMA || T.dist == MC_DIST_BETA;
-        use_clg = !lg_per_element(T.dist, T.op[1].kind, T.op[2].kind) &&
-                  !(T.op[1].kind == MC_OP_PSCALAR || T.op[2].kind == MC_OP_PSCALAR);
-    }
+    const PwElem E = pw_elem<NMAX>(T, P, i);
 
     for (int64_t r = r0; r < r1; r += kPwBatch) {
         const int kb = r1 - r < kPwBatch ? (int)(r1 - r) : kPwBatch;
@@ -296,26 +329,7 @@ __global__ __launch_bounds__(kPwBlock) void k_pointwise(PwCtx P, int64_t N, int6
 #pragma unroll 1
         for (int k = 0; k < kb; ++k) {
             const float* __restrict__ q = samples + (r + k) * D;
-            float xk = 0.0f;
-            bool done = false;
-            if constexpr (NMAX > 0) {
-                if (expr) {
-                    xk = pw_expr<NMAX>(T, P, q, i);
-                    done = true;
-                }
-            }
-            if (!done) {
-                const float v = pw_value(ov, q);
-                float m = pw_value(om, q);
-                if (aff) m = m + pw_value(ob, q) * pw_value(ox, q);
-                const float s = pw_value(os, q);
-                const float logs = need_logs ? (clogs ? T.clogs : logf(s)) : 0.0f;
-                float lg = T.clg;
-                if constexpr (LG) {
-                    if (need_lg && !use_clg) lg = lg_norm_dev(T.dist, m, s);
-                }
-                xk = T.weight * elem_eval(T.dist, T.c0, v, m, s, logs, lg).lp;
-            }
+            const float xk = pw_elem_value<NMAX, LG>(E, T, P, q, i);
             if (matrix) matrix[(r + k) * P.M + o] = xk;
             pw_lse(A, xk);
 #pragma unroll

@@ -23,9 +23,13 @@ values) or a handful of order statistics come back to the host.
   csrc/pointwise.h): the C x S x M matrix is never stored.  ``waic`` forms
   WAIC from them (Vehtari, Gelman and Gabry 2017); ``merge_pointwise`` is the
   host statement of the merge the device and the ranks apply.  Out of scope:
-  PSIS-LOO (a per-observation tail fit over draws; ``matrix=True`` hands small
-  problems to other tools) and the expression JIT for likelihoods (expression
-  terms run the node interpreter).
+  the expression JIT for likelihoods (expression terms run the node
+  interpreter).
+* ``loo(log_likelihood, samples, layout)`` — PSIS-LOO of the same kind of
+  likelihood (mc_psis_loo, csrc/psis.h): per observation an exact selection of
+  the smallest log-likelihood values over all draws, a generalized Pareto fit
+  and the smoothed leave-one-out estimate with its khat diagnostic, without
+  the matrix.  ``compare`` differences two results observation by observation.
 * ``posterior_predictive(log_likelihood, samples, layout)`` — for every
   observation of the same kind of likelihood, one replicate per kept draw from
   the term's own distribution at that draw (mc_predictive, csrc/predictive.h),
@@ -35,8 +39,8 @@ values) or a handful of order statistics come back to the host.
   the host statement of the merge.
 
 No CPU fallback: without the library these raise ``EngineUnavailable``
-(``merge_pointwise``, ``merge_predictive`` and ``waic_from_stats`` are pure
-host arithmetic).
+(``merge_pointwise``, ``merge_predictive``, ``waic_from_stats`` and ``compare``
+are pure host arithmetic).
 """
 from __future__ import annotations
 
@@ -363,6 +367,26 @@ def _pointwise_inputs(samples, layout):
     return _as_device(np.concatenate(cols, axis=2)), lay
 
 
+def _pointwise_launch(prog, x, matrix=False):
+    """mc_pointwise_stats of a pointwise program on the [C, S, D] device
+    buffer: (this rank's partial, the matrix tensor or None)."""
+    import torch
+
+    C, S, D = x.shape
+    lib = _lib.load()
+    M = prog.num_elements
+    st = torch.empty((_lib.MC_PW_COUNT, M), dtype=torch.float64, device=x.device)
+    mat = torch.empty((C, S, M), dtype=torch.float32, device=x.device) if matrix else None
+    nb = lib.mc_pointwise_workspace_bytes(prog.handle, C, S)
+    if nb < 0:
+        _lib.check(int(nb))
+    ws = torch.empty(max(int(nb), 1), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.mc_pointwise_stats(prog.handle, C, S, _lib.ptr(x), _lib.ptr(st),
+                                      _lib.ptr(mat), _lib.ptr(ws), nb, _lib.stream_handle()))
+    host = st.cpu().numpy()   # (synchronises: prog, x and ws outlive the launch)
+    return {f: host[k].copy() for k, f in enumerate(PW_FIELDS)}, mat
+
+
 def pointwise_log_likelihood(log_likelihood_fn, samples, layout=None, *, matrix=False,
                              group=None):
     """Per-observation log-likelihood statistics over the kept draws.
@@ -391,20 +415,7 @@ def pointwise_log_likelihood(log_likelihood_fn, samples, layout=None, *, matrix=
     from . import _trace
 
     x, lay = _pointwise_inputs(samples, layout)
-    C, S, D = x.shape
-    prog = _trace.pointwise_program(log_likelihood_fn, lay)
-    lib = _lib.load()
-    M = prog.num_elements
-    st = torch.empty((_lib.MC_PW_COUNT, M), dtype=torch.float64, device=x.device)
-    mat = torch.empty((C, S, M), dtype=torch.float32, device=x.device) if matrix else None
-    nb = lib.mc_pointwise_workspace_bytes(prog.handle, C, S)
-    if nb < 0:
-        _lib.check(int(nb))
-    ws = torch.empty(max(int(nb), 1), dtype=torch.uint8, device=x.device)
-    _lib.check(lib.mc_pointwise_stats(prog.handle, C, S, _lib.ptr(x), _lib.ptr(st),
-                                      _lib.ptr(mat), _lib.ptr(ws), nb, _lib.stream_handle()))
-    host = st.cpu().numpy()   # (synchronises: prog, x and ws outlive the launch)
-    part = {f: host[k].copy() for k, f in enumerate(PW_FIELDS)}
+    part, mat = _pointwise_launch(_trace.pointwise_program(log_likelihood_fn, lay), x, matrix)
     out = merge_pointwise(_gather_parts(part, group))
     if matrix:
         out["matrix"] = mat
@@ -441,8 +452,105 @@ def waic(log_likelihood_fn, samples, layout=None, *, group=None) -> dict:
                                                     group=group))
 
 
+# ------------------------------------------------------------ PSIS-LOO -----
+def _refuse_sharded_draws(group):
+    import torch.distributed as dist
+
+    if group is not False and dist.is_available() and dist.is_initialized() \
+            and dist.get_world_size(group) > 1:
+        raise ValueError("PSIS-LOO is not mergeable over shards of draws: an observation's "
+                         "tail is taken over all draws; gather the draws on one rank, or pass "
+                         "group=False for this rank's draws alone")
+
+
+def loo(log_likelihood_fn, samples, layout=None, *, r_eff=1.0, tail=False, group=None) -> dict:
+    """PSIS-LOO (Vehtari, Gelman and Gabry 2017) of a likelihood over the kept
+    draws, on the device (``pointwise_log_likelihood``'s arguments;
+    mc_psis_loo, csrc/psis.h; the definition is stated in include/mcmc355.h).
+
+    Per observation the ``tail_len`` smallest log-likelihood values over all
+    draws are selected exactly, a generalized Pareto distribution is fitted to
+    the importance ratios they imply and the tail's weights are replaced by
+    its quantiles; the C x S x M matrix is never stored.  ``r_eff`` is the
+    relative efficiency of the draws (a positive scalar) and only sets the
+    tail length.
+
+    Returns ``elpd_loo``, ``p_loo`` (= lppd - elpd_loo), ``looic``
+    (= -2 elpd_loo), ``se`` (= sqrt(M var_i elpd_loo_i)), ``lppd``, the
+    ``pointwise`` terms (``elpd_loo``, ``p_loo``, ``lppd``, ``khat``),
+    ``n_obs``, ``n_draws``, ``tail_len``, ``n_high_k`` (observations with
+    khat > 0.7, where the estimate is unreliable; +inf, a tail of at most four
+    distinct values, included) and ``n_nonfinite`` (draws outside an
+    observation's support: that observation's terms are NaN; reported, never
+    raised).  ``tail=True`` adds ``tail``, the [M, tail_len] float32 device
+    tensor of every observation's tail in ascending order (NaN past its
+    length), with ``cutoff``, ``min``, ``sigma`` and ``tail_n`` per observation.
+
+    PSIS is not mergeable over shards of draws: with an initialised process
+    group of more than one rank this raises ``ValueError`` unless
+    ``group=False`` (this rank's draws alone)."""
+    import torch
+
+    from . import _trace
+
+    _refuse_sharded_draws(group)
+    r_eff = float(r_eff)
+    if not (r_eff > 0.0 and np.isfinite(r_eff)):
+        raise ValueError("r_eff must be a positive finite scalar")
+    x, lay = _pointwise_inputs(samples, layout)
+    C, S, D = x.shape
+    prog = _trace.pointwise_program(log_likelihood_fn, lay)
+    stats, _ = _pointwise_launch(prog, x)
+    lib = _lib.load()
+    M = prog.num_elements
+    nb = lib.mc_psis_workspace_bytes(prog.handle, C, S, r_eff)
+    if nb < 0:   # (a tail beyond the kernel's capacity is reported here: nothing is launched)
+        _lib.check(int(nb))
+    mt = int(lib.mc_psis_tail_len(C * S, r_eff))
+    out = torch.empty((_lib.MC_PSIS_COUNT, M), dtype=torch.float64, device=x.device)
+    tl = torch.empty((M, mt), dtype=torch.float32, device=x.device) if tail else None
+    ws = torch.empty(max(int(nb), 8), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.mc_psis_loo(prog.handle, C, S, r_eff, _lib.ptr(x), _lib.ptr(out),
+                               _lib.ptr(tl), _lib.ptr(ws), nb, _lib.stream_handle()))
+    host = out.cpu().numpy()   # (synchronises: prog, x and ws outlive the launch)
+    with np.errstate(all="ignore"):
+        lppd_i = np.log(stats["sumexp"]) + stats["max"] - np.log(stats["n"])
+        elpd_i = host[_lib.MC_PSIS_ELPD].copy()
+        khat = host[_lib.MC_PSIS_KHAT].copy()
+        p_i = lppd_i - elpd_i
+        elpd, lppd = float(np.sum(elpd_i)), float(np.sum(lppd_i))
+        res = {"elpd_loo": elpd, "p_loo": lppd - elpd, "looic": -2.0 * elpd,
+               "se": float(np.sqrt(M * np.var(elpd_i))), "lppd": lppd,
+               "pointwise": {"elpd_loo": elpd_i, "p_loo": p_i, "lppd": lppd_i, "khat": khat},
+               "n_obs": int(M), "n_draws": int(C * S), "tail_len": mt,
+               "n_high_k": int(np.sum(khat > 0.7)),
+               "n_nonfinite": int(np.sum(stats["nonfinite"]))}
+    if tail:
+        res.update(tail=tl, cutoff=host[_lib.MC_PSIS_CUTOFF].copy(),
+                   min=host[_lib.MC_PSIS_MIN].copy(), sigma=host[_lib.MC_PSIS_SIGMA].copy(),
+                   tail_n=host[_lib.MC_PSIS_TAILN].astype(np.int64))
+    return res
+
+
+def compare(a, b) -> dict:
+    """Difference of two ``loo`` (or two ``waic``) results on the same
+    observations: ``elpd_diff`` = sum_i (elpd_a_i - elpd_b_i) and ``se_diff``
+    = sqrt(M var_i(diff_i)) (the population variance, as ``se``).  Pure host
+    arithmetic."""
+    key = "elpd_loo" if "elpd_loo" in a["pointwise"] else "elpd_waic"
+    if key not in b["pointwise"]:
+        raise ValueError("compare takes two loo results or two waic results")
+    if a["n_obs"] != b["n_obs"]:
+        raise ValueError(f"the results cover {a['n_obs']} and {b['n_obs']} observations")
+    with np.errstate(all="ignore"):
+        d = np.asarray(a["pointwise"][key], np.float64) - np.asarray(b["pointwise"][key],
+                                                                     np.float64)
+        return {"elpd_diff": float(np.sum(d)), "se_diff": float(np.sqrt(d.size * np.var(d))),
+                "n_obs": int(d.size)}
+
+
 # ------------------------------------------------- posterior predictive -----
-PP_FIELDS = ("n", "mean", "m2", "below", "nonfinite")
+PP_FIELDS =("n", "mean", "m2", "below", "nonfinite")
 
 
 def merge_predictive(parts):

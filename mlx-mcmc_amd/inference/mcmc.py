@@ -160,6 +160,12 @@ class MCMC:
         samples, layout = self._kept_draws()
         return _diag.waic(log_likelihood_fn, samples, layout, group=False)
 
+    def loo(self, log_likelihood_fn, r_eff=1.0):
+        """PSIS-LOO of ``log_likelihood_fn`` over the kept draws, with the
+        per-observation Pareto khat diagnostic (diagnostics.loo)."""
+        samples, layout = self._kept_draws()
+        return _diag.loo(log_likelihood_fn, samples, layout, r_eff=r_eff, group=False)
+
     def posterior_predictive(self, log_likelihood_fn, seed=None, thin=1, replicates=False):
         """Posterior predictive replicates of ``log_likelihood_fn``'s observations
         over the kept draws, reduced on the device to per-observation mean,
