@@ -191,8 +191,36 @@ typedef enum {
     MC_EX_GT       = 21, /* a > b  as 1 / 0 (mx.greater: a mask, no cotangent) */
     MC_EX_GE       = 22, /* a >= b                                           */
     MC_EX_LT       = 23, /* a < b                                            */
-    MC_EX_LE       = 24  /* a <= b                                           */
+    MC_EX_LE       = 24, /* a <= b                                           */
+    /* Log masses of count data (no reference code: its distributions are
+     * continuous).  y (and n) are CONST or DATA leaves — MC_ERR_UNSUPPORTED
+     * otherwise — and take no cotangent; the normalisers log C(n, y) and
+     * -lgamma(y + 1) are constants of the data and are NOT part of the node
+     * (the caller adds them as a leaf).  With
+     *   softplus(x) = max(x, 0) + log1p(exp(-|x|)),  sigma(x) = 1 / (1 + exp(-x))
+     * in f32, one rounding per operation:                                    */
+    MC_EX_BERNOULLI_LOGIT_LP = 25, /* a = y in {0, 1}, b = eta:               */
+                         /* -softplus(y != 0 ? -eta : eta); d eta = y - sigma */
+    MC_EX_BINOMIAL_LOGIT_LP = 26,  /* a = y, b = n, c = eta; n >= 0,          */
+                         /* 0 <= y <= n, both integer-valued:                 */
+                         /* y eta - n softplus(eta); d eta = y - n sigma(eta) */
+    MC_EX_POISSON_LOG_LP = 27      /* a = y >= 0 integer-valued, b = theta:   */
+                         /* e = exp(theta); y == 0 ? -e : y theta - e;        */
+                         /* d theta = y - e                                   */
+    /* Outside the support: -inf, no cotangent.  A NaN eta / theta gives NaN;
+     * infinite ones follow the formulas (IEEE).  Bernoulli: the certain
+     * outcome -0, the impossible one -inf.  Binomial: eta = +inf NaN;
+     * eta = -inf gives -inf for y > 0 and NaN for y = 0.  Poisson:
+     * theta = -inf gives -0 for y = 0 and -inf for y > 0; theta = +inf gives
+     * -inf for y = 0 and NaN for y > 0.                                      */
 } mc_expr_op;
+
+/* The count distributions of mc_discrete_log_prob / mc_predictive_draw_discrete. */
+typedef enum {
+    MC_DISCRETE_BERNOULLI = 0,   /* Bernoulli(logit eta)                      */
+    MC_DISCRETE_BINOMIAL  = 1,   /* Binomial(total, logit eta)                */
+    MC_DISCRETE_POISSON   = 2    /* Poisson(log rate eta)                     */
+} mc_discrete_kind;
 
 typedef struct mc_expr_node {
     int32_t    op;         /* mc_expr_op                                    */
@@ -327,6 +355,17 @@ int mc_dist_log_prob(int32_t dist, int64_t n,
                      const float* loc_dev, int32_t loc_bcast,
                      const float* scale_dev, int32_t scale_bcast,
                      float* out_dev, void* hip_stream);
+
+/* The count nodes' values elementwise (the device functions of
+ * MC_EX_BERNOULLI_LOGIT_LP / MC_EX_BINOMIAL_LOGIT_LP / MC_EX_POISSON_LOG_LP,
+ * without the normaliser): out[i] = node(value[i|0], total[i|0], eta[i|0]);
+ * kind is an mc_discrete_kind, eta the logit or the log rate; total may be
+ * NULL unless kind is MC_DISCRETE_BINOMIAL.  *_bcast = 1: a single element. */
+int mc_discrete_log_prob(int32_t kind, int64_t n,
+                         const float* value_dev, int32_t value_bcast,
+                         const float* total_dev, int32_t total_bcast,
+                         const float* eta_dev, int32_t eta_bcast,
+                         float* out_dev, void* hip_stream);
 
 /* ---- per-chain state ---------------------------------------------------- */
 /* State blob layout (device memory, mc_state_bytes(prog, C) bytes):
@@ -769,12 +808,46 @@ int mc_pointwise_stats(const mc_program* prog, int64_t C, int64_t S,
  *                attempts (each rejects with probability < 0.05), then NaN.
  *   Beta(a, b)   X / (X + Y), X ~ Gamma(a, 1), Y ~ Gamma(b, 1)
  * A scale, rate or shape that is <= 0 or NaN gives NaN (as a NaN loc does),
- * never a hang.  Expression and identity terms have no sampling distribution:
- * MC_ERR_UNSUPPORTED, naming the term, before any launch.
+ * never a hang.  Identity terms and expression terms have no sampling
+ * distribution — MC_ERR_UNSUPPORTED, naming the term, before any launch —
+ * except the count terms: an expression term whose root is
+ * MC_EX_BERNOULLI_LOGIT_LP / MC_EX_BINOMIAL_LOGIT_LP / MC_EX_POISSON_LOG_LP, or
+ * ADD of such a node and a CONST / DATA leaf (the normaliser) in either order.
+ * Their replicates come from the node's eta / theta (and n) at the draw — the
+ * term's nodes below the count node, evaluated as the pointwise kernel does —
+ * and the observation is the node's y.  Exact samplers (csrc/predictive.h
+ * states them in full), double arithmetic from IEEE operations only, uniforms
+ * u(w) = (w + 1/2) 2^-32:
+ *   Bernoulli    [log u01(w.x) - log(1 - u01(w.x)) < eta] (the samplers' f32 log)
+ *   Poisson      lambda = exp(theta) < 10: sequential-search inversion of
+ *                u(w.x); else Hormann's PTRS (1993), one block per attempt
+ *                (U = u(w.x) - 1/2, V = u(w.y)).  NaN for a NaN theta and for
+ *                lambda >= 2^23.
+ *   Binomial     p' = min(p, 1 - p), p = sigmoid(eta): inversion of u(w.x)
+ *                when n p' < 10, else Hormann's BTRS (1993); reflected when
+ *                p > 1/2.  NaN for a NaN eta and for n negative, non-integer
+ *                or >= 2^23.
+ * At most 32 attempts, then NaN.  An inversion's uniform resolves 2^-32:
+ * outcomes beyond the 1 - 2^-33 quantile do not occur.
  *
  * mc_predictive_draw: the scalar definition on the host (no device, no
  * allocation): *out = the replicate of observation obs under (dist, loc or
  * alpha, scale / rate / beta).  MC_ERR_UNSUPPORTED for any other dist.
+ *
+ * mc_predictive_draw_discrete: its counterpart for the count terms (kind an
+ * mc_discrete_kind, total the Binomial's n, eta the logit / log rate).
+ *
+ * mc_predictive_eq: mc_predictive plus equal_dev, NULL or [M] f64: the finite
+ * replicates EQUAL to the observation (the ties a discrete PIT needs; the five
+ * fields are unchanged).  mc_predictive is mc_predictive_eq with NULL.  The
+ * ties are counted for programs with a count term only
+ * (mc_program_num_count_terms > 0: every term of such a program is counted,
+ * the fused ones too); equal_dev on any other program is MC_ERR_UNSUPPORTED,
+ * and those programs' kernels and workspace size are what they were.  With a
+ * count term the workspace holds one more f64 per block and observation.
+ *
+ * mc_program_num_count_terms: how many terms of the pointwise view have a
+ * count sampler (known from program creation: no device, no view needed).
  *
  * mc_predictive: samples_dev is the [C, S, D] buffer; thin >= 1 processes
  * iterations s = 0, thin, 2 thin, ... of every chain (S' = ceil(S / thin); the
@@ -796,12 +869,19 @@ int mc_pointwise_stats(const mc_program* prog, int64_t C, int64_t S,
 #define MC_PP_COUNT     5
 int mc_predictive_draw(int dist, float loc_or_alpha, float scale_or_rate_or_beta,
                        uint64_t seed, uint32_t chain, uint32_t iter, uint32_t obs, float* out);
+int32_t mc_program_num_count_terms(const mc_program* prog);
+int mc_predictive_draw_discrete(int kind, float total, float eta, uint64_t seed,
+                                uint32_t chain, uint32_t iter, uint32_t obs, float* out);
 int64_t mc_predictive_workspace_bytes(const mc_program* prog, int64_t C, int64_t S,
                                       int64_t thin);
 int mc_predictive(const mc_program* prog, int64_t C, int64_t S, int64_t thin, uint64_t seed,
                   int64_t chain_offset, int64_t iter_offset, const float* samples_dev,
                   double* stats_dev, float* yrep_dev, void* workspace_dev,
                   int64_t workspace_bytes, void* hip_stream);
+int mc_predictive_eq(const mc_program* prog, int64_t C, int64_t S, int64_t thin, uint64_t seed,
+                     int64_t chain_offset, int64_t iter_offset, const float* samples_dev,
+                     double* stats_dev, double* equal_dev, float* yrep_dev,
+                     void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 
 /* ---- PSIS-LOO over kept draws (no reference code: its README roadmap lists
  * "Model comparison (WAIC, LOO)") ---------------------------------------------

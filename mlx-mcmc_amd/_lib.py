@@ -45,7 +45,8 @@ MC_DIST_EXPR = 6
 (MC_EX_LEAF, MC_EX_ADD, MC_EX_SUB, MC_EX_MUL, MC_EX_DIV, MC_EX_NEG, MC_EX_EXP, MC_EX_LOG,
  MC_EX_SQRT, MC_EX_SQUARE, MC_EX_POW, MC_EX_ABS, MC_EX_LOG1P, MC_EX_TANH, MC_EX_SIGMOID,
  MC_EX_NORMAL_LP, MC_EX_HALFNORMAL_LP, MC_EX_EXPONENTIAL_LP, MC_EX_WHERE,
- MC_EX_GAMMA_LP, MC_EX_BETA_LP, MC_EX_GT, MC_EX_GE, MC_EX_LT, MC_EX_LE) = range(25)
+ MC_EX_GAMMA_LP, MC_EX_BETA_LP, MC_EX_GT, MC_EX_GE, MC_EX_LT, MC_EX_LE,
+ MC_EX_BERNOULLI_LOGIT_LP, MC_EX_BINOMIAL_LOGIT_LP, MC_EX_POISSON_LOG_LP) = range(28)
 MC_EXPR_MAX_NODES = 32
 
 # mc_series_stats fields (include/mcmc355.h)
@@ -64,6 +65,9 @@ MC_PP_COUNT = 5
 (MC_PSIS_ELPD, MC_PSIS_KHAT, MC_PSIS_SIGMA, MC_PSIS_CUTOFF, MC_PSIS_MIN,
  MC_PSIS_TAILN) = range(6)
 MC_PSIS_COUNT = 6
+
+# mc_discrete_kind (mc_discrete_log_prob)
+MC_DISCRETE_BERNOULLI, MC_DISCRETE_BINOMIAL, MC_DISCRETE_POISSON = range(3)
 
 MC_OP_NONE = 0
 MC_OP_CONST = 1
@@ -229,6 +233,9 @@ SIGNATURES = [
     ("mc_dist_log_prob", ctypes.c_int,
      [ctypes.c_int32, ctypes.c_int64, _VP, ctypes.c_int32, _VP, ctypes.c_int32, _VP,
       ctypes.c_int32, _VP, _VP]),
+    ("mc_discrete_log_prob", ctypes.c_int,
+     [ctypes.c_int32, ctypes.c_int64, _VP, ctypes.c_int32, _VP, ctypes.c_int32, _VP,
+      ctypes.c_int32, _VP, _VP]),
     ("mc_state_bytes", ctypes.c_int64, [_VP, ctypes.c_int64]),
     ("mc_state_offsets", ctypes.c_int,
      [_VP, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
@@ -309,11 +316,18 @@ SIGNATURES = [
     ("mc_predictive_draw", ctypes.c_int,
      [ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32,
       ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float)]),
+    ("mc_program_num_count_terms", ctypes.c_int32, [_VP]),
+    ("mc_predictive_draw_discrete", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32,
+      ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float)]),
     ("mc_predictive_workspace_bytes", ctypes.c_int64,
      [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
     ("mc_predictive", ctypes.c_int,
      [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64,
       ctypes.c_int64, _VP, _VP, _VP, _VP, ctypes.c_int64, _VP]),
+    ("mc_predictive_eq", ctypes.c_int,
+     [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64,
+      ctypes.c_int64, _VP, _VP, _VP, _VP, _VP, ctypes.c_int64, _VP]),
     ("mc_psis_tail_len", ctypes.c_int64, [ctypes.c_int64, ctypes.c_double]),
     ("mc_psis_fit_host", ctypes.c_int,
      [_VP, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_double),

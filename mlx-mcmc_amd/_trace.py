@@ -671,6 +671,89 @@ def dist_expr(dist_name: str, value, loc, scale) -> "LogProbExpr":
     return expr_term(root)
 
 
+def _gammaln64(x: np.ndarray) -> np.ndarray:
+    """float64 log Gamma (math.lgamma per element: the C library's, as the
+    device's lgamma_norm)."""
+    import math
+
+    return np.vectorize(math.lgamma, otypes=[np.float64])(np.asarray(x, np.float64))
+
+
+def _is_count(x: np.ndarray) -> np.ndarray:
+    return (x >= 0) & np.isfinite(x) & (x == np.floor(x))
+
+
+def discrete_norm(kind: str, value, total=None) -> np.ndarray:
+    """The normaliser of a count log mass — log C(n, y) (Binomial),
+    -lgamma(y + 1) (Poisson), 0 (Bernoulli) — from the f32 data in float64,
+    rounded once to f32; 0 at elements outside the support (the node gives
+    -inf there)."""
+    y = np.asarray(value, np.float32).astype(np.float64)
+    if kind == "Bernoulli":
+        return np.zeros(y.shape, np.float32)
+    if kind == "Poisson":
+        ok = _is_count(y)
+        ys = np.where(ok, y, 0.0)
+        return np.where(ok, -_gammaln64(ys + 1.0), 0.0).astype(np.float32)
+    n = np.asarray(total, np.float32).astype(np.float64)
+    y, n = np.broadcast_arrays(y, n)
+    ok = _is_count(y) & _is_count(n) & (y <= n)
+    ys, ns = np.where(ok, y, 0.0), np.where(ok, n, 0.0)
+    lc = _gammaln64(ns + 1.0) - _gammaln64(ys + 1.0) - _gammaln64(ns - ys + 1.0)
+    return np.where(ok, lc, 0.0).astype(np.float32)
+
+
+_DISCRETE_OP = {"Bernoulli": _lib.MC_EX_BERNOULLI_LOGIT_LP,
+                "Binomial": _lib.MC_EX_BINOMIAL_LOGIT_LP,
+                "Poisson": _lib.MC_EX_POISSON_LOG_LP}
+
+
+def _concrete_f32(name: str, what: str, x) -> np.ndarray:
+    if is_symbolic(x):
+        raise TraceError(f"{name}: the {what} must be data or a constant (a count cannot be a "
+                         "traced parameter: HMC has no gradient through it)")
+    arr = np.asarray(_to_numpy(x))
+    if arr.dtype == object:
+        raise TraceError(f"{name}: unsupported {what}: " + _UNSUPPORTED)
+    arr = arr.astype(np.float32)
+    return arr if arr.ndim == 0 else np.ascontiguousarray(arr)
+
+
+def discrete_expr(name: str, value, total, arg, natural: bool) -> "LogProbExpr":
+    """Bernoulli / Binomial / Poisson log_prob with a traced argument: the
+    MC_EX_*_LP count node over (y[, n], eta) plus the normaliser leaf
+    (discrete_norm; CONST when scalar, left out for Bernoulli).  natural: arg
+    is the logit / log rate; otherwise it is a probability p or a rate r and
+    the node sits on eta = log p - log1p(-p) inside where(p > 0, where(p < 1,
+    ., -inf), -inf), or theta = log r inside where(r > 0, ., -inf)."""
+    op = _DISCRETE_OP[name]
+    y = _concrete_f32(name, "value", value)
+    ey = Expr.of(y)
+    ea = Expr.of(arg)
+    if natural:
+        eta = ea
+    elif name == "Poisson":
+        eta = Expr.unary(_lib.MC_EX_LOG, ea)
+    else:
+        eta = Expr.binary(_lib.MC_EX_SUB, Expr.unary(_lib.MC_EX_LOG, ea),
+                          Expr.unary(_lib.MC_EX_LOG1P, Expr.unary(_lib.MC_EX_NEG, ea)))
+    if name == "Binomial":
+        nt = _concrete_f32(name, "total_count", total)
+        en = Expr.of(nt)
+        core = Expr(op, [ey, en, eta], shape=_bshape(name, [ey.shape, en.shape, eta.shape]))
+        norm = discrete_norm(name, y, nt)
+    else:
+        core = Expr(op, [ey, eta], shape=_bshape(name, [ey.shape, eta.shape]))
+        norm = discrete_norm(name, y)
+    root = core if name == "Bernoulli" else Expr.binary(_lib.MC_EX_ADD, core, norm)
+    if not natural:
+        ninf = float("-inf")
+        if name != "Poisson":
+            root = Expr.where(ea < 1.0, root, ninf)
+        root = Expr.where(ea > 0.0, root, ninf)
+    return expr_term(root)
+
+
 @dataclass
 class Operand:
     kind: int

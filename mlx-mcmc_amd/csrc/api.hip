@@ -93,6 +93,35 @@ extern "C" int mc_dist_log_prob(int32_t dist, int64_t n, const float* v, int32_t
     return MC_OK;
 }
 
+__global__ void k_discrete(int kind, int64_t n, const float* v, int vb, const float* t, int tb,
+                           const float* e, int eb, float* out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const float y = v[vb ? 0 : i];
+        const float eta = e[eb ? 0 : i];
+        if (kind == MC_DISCRETE_BERNOULLI) out[i] = ex_bernoulli_lp(y, eta);
+        else if (kind == MC_DISCRETE_BINOMIAL) out[i] = ex_binomial_lp(y, t[tb ? 0 : i], eta);
+        else out[i] = ex_poisson_lp(y, eta);
+    }
+}
+
+extern "C" int mc_discrete_log_prob(int32_t kind, int64_t n, const float* v, int32_t vb,
+                                    const float* t, int32_t tb, const float* e, int32_t eb,
+                                    float* out, void* stream) {
+    if (kind < MC_DISCRETE_BERNOULLI || kind > MC_DISCRETE_POISSON)
+        return fail(MC_ERR_INVALID, "unknown discrete distribution %d", kind);
+    if (n < 0) return fail(MC_ERR_INVALID, "n < 0");
+    if (n == 0) return MC_OK;
+    const bool need_t = kind == MC_DISCRETE_BINOMIAL;
+    if (!v || !e || !out || (need_t && !t)) return fail(MC_ERR_INVALID, "NULL operand");
+    if (!need_t) tb = 1;  // the unused total is read as element 0 of value
+    const int64_t blocks = std::min<int64_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_discrete, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                       kind, n, v, vb, need_t ? t : v, tb, e, eb, out);
+    MC_HIP_TRY(hipGetLastError());
+    return MC_OK;
+}
+
 // ---------------------------------------------------------------------------
 // state
 // ---------------------------------------------------------------------------

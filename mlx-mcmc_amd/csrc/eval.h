@@ -961,6 +961,48 @@ MC_DEV void ex_beta_grad(float v, float a, float b, float& dv, float& da, float&
     db = ex_log(1.0f - v);
 }
 
+// Discrete log-mass nodes (include/mcmc355.h MC_EX_BERNOULLI_LOGIT_LP /
+// MC_EX_BINOMIAL_LOGIT_LP / MC_EX_POISSON_LOG_LP): the count y (and the
+// Binomial's n) are data or constants, eta / theta the traced argument; the
+// normalisers log C(n, y) and -lgamma(y + 1) are constants of the data and
+// live in a leaf the tracer adds, so no lgamma is compiled here.
+//   softplus(x) = max(x, 0) + log1p(exp(-|x|)): no overflow, one rounding per
+//   operation; -softplus(-+eta) is log sigmoid(+-eta) without the saturation
+//   of log(sigmoid(eta)) (exact 0 from |eta| ~ 17, 0 * -inf beyond).
+// Outside the support: -inf and no cotangent (elem_halfnormal's convention).
+// Inside the support a NaN eta / theta gives NaN, and infinite ones follow the
+// formulas (IEEE):
+//   Bernoulli  the certain outcome -0, the impossible one -inf
+//   Binomial   eta = +inf: NaN (inf - inf, or 0 * inf at y = 0);
+//              eta = -inf: -inf for y > 0, NaN for y = 0 (0 * -inf)
+//   Poisson    theta = -inf: -0 for y = 0, -inf for y > 0;
+//              theta = +inf: -inf for y = 0, NaN for y > 0 (inf - inf)
+// The cotangent factors are y - sigmoid(eta), y - n sigmoid(eta) and
+// y - exp(theta) at those arguments (finite but for exp(+inf)).
+MC_DEV bool ex_is_count(float y) {
+    return y >= 0.0f && y < __builtin_inff() && y == __builtin_floorf(y);
+}
+MC_DEV float ex_softplus(float x) {
+    return __builtin_fmaxf(x, 0.0f) + ex_log1p(ex_exp(-__builtin_fabsf(x)));
+}
+MC_DEV float ex_sigmoid(float x) { return ex_div(1.0f, 1.0f + ex_exp(-x)); }
+MC_DEV bool ex_bernoulli_in(float y) { return y == 0.0f || y == 1.0f; }
+MC_DEV bool ex_binomial_in(float y, float n) { return ex_is_count(n) && ex_is_count(y) && y <= n; }
+MC_DEV float ex_bernoulli_lp(float y, float eta) {
+    if (!ex_bernoulli_in(y)) return -__builtin_inff();
+    const float s = (y != 0.0f) ? -eta : eta;
+    return -ex_softplus(s);
+}
+MC_DEV float ex_binomial_lp(float y, float n, float eta) {
+    if (!ex_binomial_in(y, n)) return -__builtin_inff();
+    return y * eta - n * ex_softplus(eta);
+}
+MC_DEV float ex_poisson_lp(float y, float theta) {
+    if (!ex_is_count(y)) return -__builtin_inff();
+    const float e = ex_exp(theta);
+    return (y == 0.0f) ? -e : y * theta - e;
+}
+
 // Forward value of a non-leaf node (x, y, z: its argument values; c0: the
 // distribution nodes' f32 normaliser, as elem_normal / elem_halfnormal).
 // Divisions go through ex_div, exp / log / log1p through ex_exp / ex_log /
@@ -993,6 +1035,9 @@ MC_DEV float ex_fwd(int op, float x, float y, float z, float c0) {
         case MC_EX_GE: return x >= y ? 1.0f : 0.0f;
         case MC_EX_LT: return x < y ? 1.0f : 0.0f;
         case MC_EX_LE: return x <= y ? 1.0f : 0.0f;
+        case MC_EX_BERNOULLI_LOGIT_LP: return ex_bernoulli_lp(x, y);
+        case MC_EX_BINOMIAL_LOGIT_LP: return ex_binomial_lp(x, y, z);
+        case MC_EX_POISSON_LOG_LP: return ex_poisson_lp(x, y);
         default: return 0.0f;
     }
 }
@@ -1055,6 +1100,16 @@ MC_DEV void ex_bwd(int op, float x, float y, float z, float v, float c, float c0
             dz = c * gb;
             break;
         }
+        // the count nodes: nothing to y (or n), and nothing outside the support
+        case MC_EX_BERNOULLI_LOGIT_LP:
+            if (ex_bernoulli_in(x)) dy = c * (x - ex_sigmoid(y));
+            break;
+        case MC_EX_BINOMIAL_LOGIT_LP:
+            if (ex_binomial_in(x, y)) dz = c * (x - y * ex_sigmoid(z));
+            break;
+        case MC_EX_POISSON_LOG_LP:
+            if (ex_is_count(x)) dy = c * (x - ex_exp(y));
+            break;
         default: break;
     }
 }
@@ -1120,6 +1175,30 @@ MC_DEV void ex2_normal_grad(exf2 v, exf2 m, exf2 s, exf2& dv, exf2& dm, exf2& ds
     ds = ex2_div(d2, var * s) - ex2_div(exf2{1.0f, 1.0f}, s);
 }
 
+// ex_bernoulli_lp / ex_poisson_lp and their cotangent factors on a pair.
+MC_DEV exf2 ex2_bernoulli_lp(exf2 y, exf2 eta) {
+    const exf2 s = {y.x != 0.0f ? -eta.x : eta.x, y.y != 0.0f ? -eta.y : eta.y};
+    const exf2 a = {__builtin_fabsf(s.x), __builtin_fabsf(s.y)};
+    const exf2 m = {__builtin_fmaxf(s.x, 0.0f), __builtin_fmaxf(s.y, 0.0f)};
+    const exf2 r = -(m + ex2_log1p(ex2_exp(-a)));
+    return exf2{ex_bernoulli_in(y.x) ? r.x : -__builtin_inff(),
+                ex_bernoulli_in(y.y) ? r.y : -__builtin_inff()};
+}
+MC_DEV exf2 ex2_bernoulli_vjp(exf2 c, exf2 y, exf2 eta) {
+    const exf2 d = c * (y - ex2_div(exf2{1.0f, 1.0f}, 1.0f + ex2_exp(-eta)));
+    return exf2{ex_bernoulli_in(y.x) ? d.x : 0.0f, ex_bernoulli_in(y.y) ? d.y : 0.0f};
+}
+MC_DEV exf2 ex2_poisson_lp(exf2 y, exf2 theta) {
+    const exf2 e = ex2_exp(theta);
+    const exf2 r = y * theta - e;
+    return exf2{!ex_is_count(y.x) ? -__builtin_inff() : (y.x == 0.0f ? -e.x : r.x),
+                !ex_is_count(y.y) ? -__builtin_inff() : (y.y == 0.0f ? -e.y : r.y)};
+}
+MC_DEV exf2 ex2_poisson_vjp(exf2 c, exf2 y, exf2 theta) {
+    const exf2 d = c * (y - ex2_exp(theta));
+    return exf2{ex_is_count(y.x) ? d.x : 0.0f, ex_is_count(y.y) ? d.y : 0.0f};
+}
+
 MC_DEV exf2 ex2_fwd(int op, exf2 x, exf2 y, exf2 z, float c0) {
     switch (op) {
         case MC_EX_ADD: return x + y;
@@ -1133,6 +1212,8 @@ MC_DEV exf2 ex2_fwd(int op, exf2 x, exf2 y, exf2 z, float c0) {
         case MC_EX_LOG1P: return ex2_log1p(x);
         case MC_EX_SIGMOID: return ex2_div(exf2{1.0f, 1.0f}, 1.0f + ex2_exp(-x));
         case MC_EX_NORMAL_LP: return ex2_normal_lp(c0, x, y, z);
+        case MC_EX_BERNOULLI_LOGIT_LP: return ex2_bernoulli_lp(x, y);
+        case MC_EX_POISSON_LOG_LP: return ex2_poisson_lp(x, y);
         default:  // the rest per component through the scalar path
             return exf2{ex_fwd(op, x.x, y.x, z.x, c0), ex_fwd(op, x.y, y.y, z.y, c0)};
     }
@@ -1160,6 +1241,8 @@ MC_DEV void ex2_bwd(int op, exf2 x, exf2 y, exf2 z, exf2 v, exf2 c, float c0, ex
             dz = c * gs;
             break;
         }
+        case MC_EX_BERNOULLI_LOGIT_LP: dy = ex2_bernoulli_vjp(c, x, y); break;
+        case MC_EX_POISSON_LOG_LP: dy = ex2_poisson_vjp(c, x, y); break;
         default: {
             float ax, ay, az, bx, by, bz;
             ex_bwd(op, x.x, y.x, z.x, v.x, c.x, c0, ax, ay, az);

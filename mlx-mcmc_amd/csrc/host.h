@@ -178,6 +178,7 @@ struct mc_program {
     // h_data / h_index — in the caller's element order; its device tables
     // (PwView) exist only after mc_program_enable_pointwise
     std::vector<DevTerm> pw_terms;
+    std::vector<PwSampler> pw_samplers;  // one per pw_term (kind -1: none, every fused term)
     int64_t pw_n_data = 0, pw_n_index = 0;
     void* pw = nullptr;
 };

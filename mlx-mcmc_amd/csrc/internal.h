@@ -82,6 +82,16 @@ struct DevExprNode {
     DevOperand leaf;
 };
 
+// The sampling distribution of an expression term of the pointwise view whose
+// root is a count node, or ADD(count node, CONST | DATA leaf) in either order
+// (recorded at program creation; predictive.h draws its replicates): kind an
+// mc_discrete_kind or -1 (no sampling distribution), node the count node, y /
+// tot / eta its argument nodes (tot -1 unless Binomial) — indices within the
+// term, all below `node`.
+struct PwSampler {
+    int32_t kind, node, y, tot, eta;
+};
+
 struct DevCtx {
     const DevTerm* terms;
     const DevExprNode* nodes;  // expression-term nodes (may be null)

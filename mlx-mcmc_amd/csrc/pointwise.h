@@ -214,11 +214,10 @@ MC_DEV float pw_value(const PwOp& r, const float* __restrict__ q) {
 // eval_expr_n's forward half on the nodes as validated: original pools, no
 // run layout).  NMAX 16 keeps val[] in registers; 32 may spill to scratch.
 template <int NMAX>
-MC_DEV float pw_expr(const DevTerm& T, const PwCtx& P, const float* __restrict__ q, int64_t i) {
+MC_DEV void pw_expr_walk(const DevTerm& T, const PwCtx& P, const float* __restrict__ q, int64_t i,
+                         int stop, float (&val)[NMAX]) {
     const MC_CONST DevExprNode* N = cptr(P.nodes) + T.expr_base;
-    const int nn = T.expr_n;
-    float val[NMAX];
-    for (int k = 0; k < nn && k < NMAX; ++k) {
+    for (int k = 0; k < stop && k < NMAX; ++k) {
         const int op = N[k].op;
         float v;
         if (op == MC_EX_LEAF) {
@@ -237,6 +236,14 @@ MC_DEV float pw_expr(const DevTerm& T, const PwCtx& P, const float* __restrict__
         }
         val[k] = v;
     }
+}
+// (stop: the nodes [0, stop) are evaluated — the whole term here; predictive.h
+// stops before a count node to read its arguments)
+template <int NMAX>
+MC_DEV float pw_expr(const DevTerm& T, const PwCtx& P, const float* __restrict__ q, int64_t i) {
+    const int nn = T.expr_n;
+    float val[NMAX];
+    pw_expr_walk<NMAX>(T, P, q, i, nn, val);
     return T.weight * val[nn - 1];
 }
 

@@ -38,6 +38,58 @@
 //              loc does): never a hang — the attempt loop has a compile-time
 //              bound.
 //
+//   count terms  an expression term whose root is a count node of eval.h
+//             (MC_EX_BERNOULLI_LOGIT_LP / MC_EX_BINOMIAL_LOGIT_LP /
+//             MC_EX_POISSON_LOG_LP), or ADD(that node, a CONST / DATA leaf),
+//             has a sampling distribution (internal.h PwSampler, recorded at
+//             program creation): per draw the term's nodes below the count
+//             node are evaluated (pw_expr_walk: eta / theta, n and the
+//             observed y are node values) and pp_draw_discrete draws the
+//             replicate.  Exact samplers, no normal approximation; every loop
+//             has a compile-time bound and exhaustion gives NaN.  Their
+//             uniforms are u(w) = (w + 1/2) 2^-32 in double (mc_u01_f64):
+//             resolution 2^-32, so an inversion cannot return an outcome
+//             beyond the 1 - 2^-33 quantile.  exp and log are pp_exp / pp_log
+//             below: double, from +, -, *, /, rint, frexp and ldexp alone, so
+//             host and device take the same decisions.
+//     Bernoulli(eta)    y = [log u - log(1 - u) < eta], u = mc_u01_boxf(w.x)
+//                  (24-bit significand: 1 - u has resolution 2^-24; u rounds
+//                  to 1 with probability 2^-25 and then y = 0), both logs
+//                  mc_logf_unit: no exponential.  NaN eta: NaN.
+//     Poisson(theta)    lambda = pp_exp(theta); NaN when lambda is NaN or
+//                  >= 2^23 (an f32 count is no longer exact), 0 when lambda
+//                  is 0.  lambda < 10: sequential search from 0 on u(w.x) of
+//                  attempt 0 through p_0 = exp(-lambda), p_k = p_(k-1)
+//                  lambda / k (at most kPpInvMax terms).  Else Hormann's PTRS
+//                  ("The transformed rejection method for generating Poisson
+//                  random variables", 1993): b = 0.931 + 2.53 sqrt(lambda),
+//                  a = -0.059 + 0.02483 b, 1/alpha = 1.1239 + 1.1328 / (b -
+//                  3.4), vr = 0.9277 - 3.6224 / (b - 2); per attempt U = u(w.x)
+//                  - 1/2, V = u(w.y), us = 1/2 - |U|, k = floor((2 a / us + b)
+//                  U + lambda + 0.43); accept when us >= 0.07 and V <= vr;
+//                  reject when k < 0 or (us < 0.013 and V > us); else accept
+//                  when log(V / alpha / (a / us^2 + b)) <= k log lambda -
+//                  lambda - log k!.
+//     Binomial(n, eta)  NaN for a NaN eta and for n negative, non-integer or
+//                  >= 2^23.  e = pp_exp(-|eta|), q = 1 / (1 + e), p = e q =
+//                  min(sigma(eta), 1 - sigma(eta)); the count k of the rarer
+//                  outcome is drawn and reflected (n - k) when eta > 0.
+//                  n p < 10: sequential search from 0 on u(w.x) through p_0 =
+//                  q^n, p_(k+1) = p_k e (n - k) / (k + 1) (k = n ends it).
+//                  Else Hormann's BTRS ("The generation of binomial random
+//                  variates", 1993): s = sqrt(n p q), b = 1.15 + 2.53 s, a =
+//                  -0.0873 + 0.0248 b + 0.01 p, c = n p + 1/2, vr = 0.92 -
+//                  4.2 / b, alpha = (2.83 + 5.1 / b) s, m = floor((n + 1) p);
+//                  per attempt U, V, us as above, k = floor((2 a / us + b) U
+//                  + c); accept when us >= 0.07 and V <= vr; reject when k < 0
+//                  or k > n; else accept when log(V alpha / (a / us^2 + b)) <=
+//                  log m! + log (n - m)! - log k! - log (n - k)! + (k - m)
+//                  log(p / q), log(p / q) = -|eta|.
+//     log k!       a table below 10, else Stirling's series of lgamma(k + 1)
+//                  to the 1 / x^7 term (error below 1e-12).
+//     At most kPpAttempts attempts (PTRS and BTRS accept more than two in
+//     three), then NaN.
+//
 //   k_predictive<GB>  grid (tiles, B) on the pointwise view (pointwise.h PwCtx,
 //                 tiles of <= 256 consecutive elements of one term), one
 //                 observation per thread, its operands decoded once into
@@ -55,6 +107,11 @@
 //                 at that draw).  No LDS, no atomics, nothing between
 //                 workgroups.  GB = true carries the Gamma / Beta rejection
 //                 loop; GB = false (programs without such terms) does not.
+//                 NMAX = 16 / 32 (programs with count terms of up to that many
+//                 nodes, or a caller that asks for the ties) adds the count
+//                 terms' path and EQUAL, the finite replicates equal to the
+//                 observation (a sixth f64 per observation, kept apart from
+//                 the five fields); NMAX = 0 is the kernel without either.
 //   k_pp_merge    one thread per observation merges the B partials in block
 //                 order.
 // B and the tiling depend on (C, S, thin, the program) only — never on the
@@ -123,6 +180,198 @@ MC_HD float pp_draw(int dist, float m, float s, uint64_t seed, uint32_t chain, u
     return pp_nan();
 }
 
+// ---- count samplers ------------------------------------------------------
+constexpr int kPpInvMax = 128;  // terms of a sequential search (means below 10)
+
+// exp(x) in double from IEEE operations: x = k ln 2 + r, |r| <= ln 2 / 2,
+// Taylor's series of exp(r) to r^13 (4e-18), scaled by 2^k.  0 below -700,
+// +inf above 700, NaN for NaN.
+MC_HD double pp_exp(double x) {
+    if (x != x) return x;
+    if (x < -700.0) return 0.0;
+    if (x > 700.0) return (double)__builtin_inff();
+    const double k = rint(x * 1.4426950408889634);
+    const double r = (x - k * 6.93147180369123816490e-01) - k * 1.90821492927058770002e-10;
+    double p = 1.0 / 6227020800.0;
+    p = p * r + 1.0 / 479001600.0;
+    p = p * r + 1.0 / 39916800.0;
+    p = p * r + 1.0 / 3628800.0;
+    p = p * r + 1.0 / 362880.0;
+    p = p * r + 1.0 / 40320.0;
+    p = p * r + 1.0 / 5040.0;
+    p = p * r + 1.0 / 720.0;
+    p = p * r + 1.0 / 120.0;
+    p = p * r + 1.0 / 24.0;
+    p = p * r + 1.0 / 6.0;
+    p = p * r + 0.5;
+    p = p * r + 1.0;
+    p = p * r + 1.0;
+    return ldexp(p, (int)k);
+}
+// log(x) in double, x positive, finite and normal: x = m 2^k, m in [sqrt(2) / 2,
+// sqrt(2)), s = (m - 1) / (m + 1), log m = 2 atanh(s) to s^25 (1e-20).
+MC_HD double pp_log(double x) {
+    int k;
+    double m = frexp(x, &k);
+    if (m < 0.70710678118654752) {
+        m = m * 2.0;
+        k -= 1;
+    }
+    const double f = m - 1.0;
+    const double s = f / (2.0 + f);
+    const double z = s * s;
+    double p = 1.0 / 25.0;
+    p = p * z + 1.0 / 23.0;
+    p = p * z + 1.0 / 21.0;
+    p = p * z + 1.0 / 19.0;
+    p = p * z + 1.0 / 17.0;
+    p = p * z + 1.0 / 15.0;
+    p = p * z + 1.0 / 13.0;
+    p = p * z + 1.0 / 11.0;
+    p = p * z + 1.0 / 9.0;
+    p = p * z + 1.0 / 7.0;
+    p = p * z + 1.0 / 5.0;
+    p = p * z + 1.0 / 3.0;
+    p = p * z + 1.0;
+    const double dk = (double)k;
+    return dk * 6.93147180369123816490e-01 + (dk * 1.90821492927058770002e-10 + 2.0 * s * p);
+}
+// log k!, k a non-negative integer value.
+MC_HD double pp_logfact(double k) {
+    if (k < 10.0) {
+        const int j = (int)k;
+        return j < 2 ? 0.0
+             : j == 2 ? 0.693147180559945309
+             : j == 3 ? 1.791759469228055001
+             : j == 4 ? 3.178053830347945620
+             : j == 5 ? 4.787491742782045994
+             : j == 6 ? 6.579251212010100995
+             : j == 7 ? 8.525161361065414300
+             : j == 8 ? 10.60460290274525023
+                      : 12.80182748008146961;
+    }
+    const double x = k + 1.0;
+    const double r = 1.0 / x, r2 = r * r;
+    const double c = r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0 - r2 * (1.0 / 1680.0))));
+    return ((x - 0.5) * pp_log(x) - x) + (0.918938533204672742 + c);
+}
+
+MC_HD float pp_bernoulli(float eta, uint64_t seed, uint32_t chain, uint32_t iter, uint32_t obs) {
+    if (eta != eta) return pp_nan();
+    const mc_u32x4 w = mc_draw(seed, chain, iter, MC_RNG_TAG_PREDICT, 0u, obs);
+    const float u = mc_u01_boxf(w.x);
+    const float um = 1.0f - u;
+    if (!(um > 0.0f)) return 0.0f;  // (the logit of u = 1 is +inf)
+    return (mc_logf_unit(u) - mc_logf_unit(um) < eta) ? 1.0f : 0.0f;
+}
+
+MC_HD float pp_poisson(float theta, uint64_t seed, uint32_t chain, uint32_t iter, uint32_t obs) {
+    const double lam = pp_exp((double)theta);
+    if (!(lam < 8388608.0)) return pp_nan();
+    if (lam == 0.0) return 0.0f;
+    float out = pp_nan();
+    if (lam < 10.0) {
+        const mc_u32x4 w = mc_draw(seed, chain, iter, MC_RNG_TAG_PREDICT, 0u, obs);
+        const double u = mc_u01_f64(w.x);
+        double pk = pp_exp(-lam), F = pk;
+#pragma unroll 1
+        for (int k = 0; k < kPpInvMax; ++k) {
+            if (u <= F) {
+                out = (float)k;
+                break;
+            }
+            pk = pk * lam / (double)(k + 1);
+            F += pk;
+        }
+        return out;
+    }
+    const double slam = sqrt(lam), loglam = pp_log(lam);
+    const double b = 0.931 + 2.53 * slam;
+    const double a = -0.059 + 0.02483 * b;
+    const double invalpha = 1.1239 + 1.1328 / (b - 3.4);
+    const double vr = 0.9277 - 3.6224 / (b - 2.0);
+#pragma unroll 1
+    for (int t = 0; t < kPpAttempts; ++t) {
+        const mc_u32x4 w = mc_draw(seed, chain, iter, MC_RNG_TAG_PREDICT, (uint32_t)t, obs);
+        const double U = mc_u01_f64(w.x) - 0.5, V = mc_u01_f64(w.y);
+        const double us = 0.5 - fabs(U);
+        const double k = floor((2.0 * a / us + b) * U + lam + 0.43);
+        if (us >= 0.07 && V <= vr) {
+            out = (float)k;
+            break;
+        }
+        if (k < 0.0 || (us < 0.013 && V > us)) continue;
+        if (pp_log(V * invalpha / (a / (us * us) + b)) <= (k * loglam - lam) - pp_logfact(k)) {
+            out = (float)k;
+            break;
+        }
+    }
+    return out;
+}
+
+MC_HD float pp_binomial(float nf, float eta, uint64_t seed, uint32_t chain, uint32_t iter,
+                        uint32_t obs) {
+    if (!(nf >= 0.0f) || !(nf < 8388608.0f) || nf != floorf(nf) || eta != eta) return pp_nan();
+    const double n = (double)nf;
+    const double ae = fabs((double)eta);
+    const double e = pp_exp(-ae);  // p / q of the rarer outcome
+    const double q = 1.0 / (1.0 + e), p = e * q;
+    double kk = -1.0;
+    if (n * p < 10.0) {
+        const mc_u32x4 w = mc_draw(seed, chain, iter, MC_RNG_TAG_PREDICT, 0u, obs);
+        const double u = mc_u01_f64(w.x);
+        double pk = pp_exp(n * pp_log(q)), F = pk;
+#pragma unroll 1
+        for (int k = 0; k < kPpInvMax; ++k) {
+            const double dk = (double)k;
+            if (u <= F || dk >= n) {
+                kk = dk;
+                break;
+            }
+            pk = pk * e * ((n - dk) / (dk + 1.0));
+            F += pk;
+        }
+    } else {
+        const double spq = sqrt(n * p * q);
+        const double b = 1.15 + 2.53 * spq;
+        const double a = -0.0873 + 0.0248 * b + 0.01 * p;
+        const double c = n * p + 0.5;
+        const double vr = 0.92 - 4.2 / b;
+        const double alpha = (2.83 + 5.1 / b) * spq;
+        const double m = floor((n + 1.0) * p);
+        const double hm = pp_logfact(m) + pp_logfact(n - m);
+#pragma unroll 1
+        for (int t = 0; t < kPpAttempts; ++t) {
+            const mc_u32x4 w = mc_draw(seed, chain, iter, MC_RNG_TAG_PREDICT, (uint32_t)t, obs);
+            const double U = mc_u01_f64(w.x) - 0.5, V = mc_u01_f64(w.y);
+            const double us = 0.5 - fabs(U);
+            const double k = floor((2.0 * a / us + b) * U + c);
+            if (k < 0.0 || k > n) continue;
+            if (us >= 0.07 && V <= vr) {
+                kk = k;
+                break;
+            }
+            if (pp_log(V * alpha / (a / (us * us) + b)) <=
+                ((hm - pp_logfact(k)) - pp_logfact(n - k)) - (k - m) * ae) {
+                kk = k;
+                break;
+            }
+        }
+    }
+    if (kk < 0.0) return pp_nan();
+    return (float)(eta > 0.0f ? n - kk : kk);
+}
+
+// The replicate of one observation of a count term: kind an mc_discrete_kind,
+// eta the logit / log rate, total the Binomial's n.
+MC_HD float pp_draw_discrete(int kind, float total, float eta, uint64_t seed, uint32_t chain,
+                             uint32_t iter, uint32_t obs) {
+    if (kind == MC_DISCRETE_BERNOULLI) return pp_bernoulli(eta, seed, chain, iter, obs);
+    if (kind == MC_DISCRETE_BINOMIAL) return pp_binomial(total, eta, seed, chain, iter, obs);
+    if (kind == MC_DISCRETE_POISSON) return pp_poisson(eta, seed, chain, iter, obs);
+    return pp_nan();
+}
+
 #if defined(__HIPCC__)
 #include "pointwise.h"
 
@@ -138,11 +387,13 @@ struct PpRun {
     uint32_t chain0, iter0;
 };
 
-template <bool GB>
+template <bool GB, int NMAX>
 __global__ __launch_bounds__(kPwBlock) void k_predictive(PwCtx P, PpRun R,
                                                          const float* __restrict__ samples,
                                                          double* __restrict__ part,
-                                                         float* __restrict__ yrep) {
+                                                         float* __restrict__ yrep,
+                                                         const PwSampler* __restrict__ samp,
+                                                         double* __restrict__ eqpart) {
     const PwTile tile = P.tiles[blockIdx.x];
     const DevTerm T = load_term(cptr(P.terms) + __builtin_amdgcn_readfirstlane(tile.term));
     const int64_t i = tile.e0 + threadIdx.x;
@@ -162,8 +413,22 @@ __global__ __launch_bounds__(kPwBlock) void k_predictive(PwCtx P, PpRun R,
         ox = pw_operand(T.ax, i, P);
     }
 
+    // a count term (wave-uniform, as the tile's term): its sampler
+    PwSampler sd = {-1, -1, -1, -1, -1};
+    if constexpr (NMAX > 0) {
+        if (T.dist == MC_DIST_EXPR) {
+            const MC_CONST PwSampler* sp = cptr(samp) + __builtin_amdgcn_readfirstlane(tile.term);
+            sd.kind = sp->kind;
+            sd.node = sp->node;
+            sd.y = sp->y;
+            sd.tot = sp->tot;
+            sd.eta = sp->eta;
+        }
+    }
+
     PwAcc A = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     double nfsum = 0.0, below = 0.0;
+    [[maybe_unused]] double equal = 0.0;
     // (one division per block; the walk below steps (c, k) without one)
     int64_t c = p0 / R.Sp, k = p0 - c * R.Sp;
     for (int64_t p = p0; p < p1; p += kPwBatch) {
@@ -175,16 +440,33 @@ __global__ __launch_bounds__(kPwBlock) void k_predictive(PwCtx P, PpRun R,
         for (int b = 0; b < kb; ++b) {
             const int64_t s = k * R.thin;
             const float* __restrict__ q = samples + (c * R.S + s) * D;
-            const float v = pw_value(ov, q);
-            float m = pw_value(om, q);
-            if (aff) m = m + pw_value(ob, q) * pw_value(ox, q);
-            const float sc = pw_value(os, q);
-            const float y = pp_draw<GB>(T.dist, m, sc, R.seed, R.chain0 + (uint32_t)c,
-                                        R.iter0 + (uint32_t)s, (uint32_t)o);
+            float v = 0.0f, y = 0.0f;
+            bool count_term = false;
+            if constexpr (NMAX > 0) count_term = sd.kind >= 0;
+            if (count_term) {
+                if constexpr (NMAX > 0) {
+                    float val[NMAX];
+                    pw_expr_walk<NMAX>(T, P, q, i, sd.node, val);
+                    v = val[sd.y];
+                    y = pp_draw_discrete(sd.kind, sd.tot >= 0 ? val[sd.tot] : 0.0f, val[sd.eta],
+                                         R.seed, R.chain0 + (uint32_t)c, R.iter0 + (uint32_t)s,
+                                         (uint32_t)o);
+                }
+            } else {
+                v = pw_value(ov, q);
+                float m = pw_value(om, q);
+                if (aff) m = m + pw_value(ob, q) * pw_value(ox, q);
+                const float sc = pw_value(os, q);
+                y = pp_draw<GB>(T.dist, m, sc, R.seed, R.chain0 + (uint32_t)c,
+                                R.iter0 + (uint32_t)s, (uint32_t)o);
+            }
             if (yrep) yrep[(p + b) * P.M + o] = y;
-            // (a non-finite y compares false or is dropped here: BELOW counts
-            // finite replicates only)
+            // (a non-finite y compares false or is dropped here: BELOW and
+            // EQUAL count finite replicates only)
             if (y - y == 0.0f && y < v) below += 1.0;
+            if constexpr (NMAX > 0) {
+                if (y - y == 0.0f && y == v) equal += 1.0;
+            }
 #pragma unroll
             for (int j = 0; j + 1 < kPwBatch; ++j) x[j] = x[j + 1];
             x[kPwBatch - 1] = y;
@@ -202,6 +484,9 @@ __global__ __launch_bounds__(kPwBlock) void k_predictive(PwCtx P, PpRun R,
     out[PP_M2 * P.M] = A.m2;
     out[PP_BELOW * P.M] = below;
     out[PP_NONFINITE * P.M] = A.nf;
+    if constexpr (NMAX > 0) {
+        if (eqpart) eqpart[(int64_t)blockIdx.y * P.M + o] = equal;
+    }
 }
 
 // stats[f * M + o] from the B partials of observation o, in block order:
@@ -209,9 +494,16 @@ __global__ __launch_bounds__(kPwBlock) void k_predictive(PwCtx P, PpRun R,
 // leaves the other's moments), counts added.
 static __global__ __launch_bounds__(256) void k_pp_merge(const double* __restrict__ part,
                                                          int64_t M, int32_t B,
-                                                         double* __restrict__ stats) {
+                                                         double* __restrict__ stats,
+                                                         const double* __restrict__ eqpart,
+                                                         double* __restrict__ equal) {
     const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= M) return;
+    if (equal) {  // (counts: exact in any order)
+        double e = 0.0;
+        for (int b = 0; b < B; ++b) e += eqpart[(int64_t)b * M + o];
+        equal[o] = e;
+    }
     const double* p = part + o;
     double n = p[PP_N * M], mean = p[PP_MEAN * M], m2 = p[PP_M2 * M], below = p[PP_BELOW * M],
            nf = p[PP_NONFINITE * M];

@@ -433,7 +433,7 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
         d.c = s.c;
         d.leaf.kind = MC_OP_NONE;
         d.leaf.slot = -1;
-        if (s.op < MC_EX_LEAF || s.op > MC_EX_LE)
+        if (s.op < MC_EX_LEAF || s.op > MC_EX_POISSON_LOG_LP)
             return fail(MC_ERR_INVALID, "term %d node %d: unknown op %d", t, k, s.op);
         if (s.op == MC_EX_LEAF) {
             const mc_operand& o = s.leaf;
@@ -489,9 +489,11 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
         switch (s.op) {
             case MC_EX_ADD: case MC_EX_SUB: case MC_EX_MUL: case MC_EX_DIV: case MC_EX_POW:
             case MC_EX_GT: case MC_EX_GE: case MC_EX_LT: case MC_EX_LE:
+            case MC_EX_BERNOULLI_LOGIT_LP: case MC_EX_POISSON_LOG_LP:
                 ub = true;
                 break;
             case MC_EX_NORMAL_LP: case MC_EX_WHERE: case MC_EX_GAMMA_LP: case MC_EX_BETA_LP:
+            case MC_EX_BINOMIAL_LOGIT_LP:
                 ub = uc = true;
                 break;
             case MC_EX_HALFNORMAL_LP: case MC_EX_EXPONENTIAL_LP:
@@ -510,6 +512,21 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
             !(en[s.a].op >= MC_EX_GT && en[s.a].op <= MC_EX_LE))
             return fail(MC_ERR_UNSUPPORTED, "term %d node %d: a where mask must be data, a "
                         "constant or a comparison", t, k);
+        // the count nodes' y (and the Binomial's n): data or a constant
+        if (s.op >= MC_EX_BERNOULLI_LOGIT_LP && s.op <= MC_EX_POISSON_LOG_LP) {
+            auto fixed = [&](int x) {
+                return en[x].op == MC_EX_LEAF &&
+                       (en[x].leaf.kind == MC_OP_CONST || en[x].leaf.kind == MC_OP_DATA);
+            };
+            static const char* const names[] = {"Bernoulli", "Binomial", "Poisson"};
+            const char* nm = names[s.op - MC_EX_BERNOULLI_LOGIT_LP];
+            if (!fixed(s.a))
+                return fail(MC_ERR_UNSUPPORTED, "term %d node %d: the %s node's count y must be "
+                            "data or a constant", t, k, nm);
+            if (s.op == MC_EX_BINOMIAL_LOGIT_LP && !fixed(s.b))
+                return fail(MC_ERR_UNSUPPORTED, "term %d node %d: the Binomial node's total n "
+                            "must be data or a constant", t, k);
+        }
         // the distribution nodes' f32 normalisers (elem_normal / elem_halfnormal)
         if (s.op == MC_EX_NORMAL_LP) d.leaf.cval = dist_c0(MC_DIST_NORMAL);
         if (s.op == MC_EX_HALFNORMAL_LP) d.leaf.cval = dist_c0(MC_DIST_HALFNORMAL);
@@ -632,6 +649,32 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
     return MC_OK;
 }
 
+// The sampler descriptor of an expression term (internal.h PwSampler) from its
+// validated nodes.
+static PwSampler expr_sampler(const DevExprNode* N, int nn) {
+    PwSampler sd = {-1, -1, -1, -1, -1};
+    auto count_node = [](int op) {
+        return op >= MC_EX_BERNOULLI_LOGIT_LP && op <= MC_EX_POISSON_LOG_LP;
+    };
+    auto fixed_leaf = [&](int k) {
+        return N[k].op == MC_EX_LEAF &&
+               (N[k].leaf.kind == MC_OP_CONST || N[k].leaf.kind == MC_OP_DATA);
+    };
+    int node = -1;
+    const DevExprNode& r = N[nn - 1];
+    if (count_node(r.op)) node = nn - 1;
+    else if (r.op == MC_EX_ADD && count_node(N[r.a].op) && fixed_leaf(r.b)) node = r.a;
+    else if (r.op == MC_EX_ADD && count_node(N[r.b].op) && fixed_leaf(r.a)) node = r.b;
+    if (node < 0) return sd;
+    const DevExprNode& d = N[node];
+    sd.kind = d.op - MC_EX_BERNOULLI_LOGIT_LP;  // mc_discrete_kind, in op order
+    sd.node = node;
+    sd.y = d.a;
+    sd.tot = d.op == MC_EX_BINOMIAL_LOGIT_LP ? d.b : -1;
+    sd.eta = d.op == MC_EX_BINOMIAL_LOGIT_LP ? d.c : d.b;
+    return sd;
+}
+
 extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
                                       const mc_affine* affines, int32_t n_affines,
                                       const mc_expr* exprs, int32_t n_exprs,
@@ -653,6 +696,7 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
     std::vector<float> dpool(data, data + n_data);
     std::vector<int32_t> ipool(index, index + n_index);
     std::vector<DevTerm> dts, raws, pws;  // pws: the pointwise view (host.h pw_terms)
+    std::vector<PwSampler> pwsd;          // and its samplers (host.h pw_samplers)
     std::vector<DevExprNode> gnodes, rnodes;
     int64_t max_n = 0;
     for (int32_t t = 0; t < n_terms; ++t) max_n = std::max<int64_t>(max_n, terms[t].n);
@@ -673,6 +717,7 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
             if (rc) return rc;
             raws.push_back(dt);
             pws.push_back(dt);
+            pwsd.push_back(expr_sampler(rnodes.data() + dt.expr_base, dt.expr_n));
             dts.push_back(dt);
             continue;
         }
@@ -834,6 +879,7 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
         pwt.clogs = dt.clogs;
         pwt.clg = dt.clg;
         pws.push_back(pwt);
+        pwsd.push_back(PwSampler{-1, -1, -1, -1, -1});
         // pass planning: accumulating vector operands with overlapping parameter
         // ranges go to different sweeps
         int64_t lo[3], hi[3];
@@ -1030,6 +1076,7 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
     p->nodes = gnodes;
     p->rnodes = rnodes;
     p->pw_terms = pws;
+    p->pw_samplers = pwsd;
     p->pw_n_data = n_data;
     p->pw_n_index = n_index;
     p->ex = !gnodes.empty();

@@ -10,6 +10,7 @@ struct PwView {
     float* d_data = nullptr;
     int32_t* d_index = nullptr;
     PwTile* d_tiles = nullptr;
+    PwSampler* d_samplers = nullptr;  // one per term (internal.h; predictive.h reads them)
     int32_t ntiles = 0;
     int64_t M = 0;
     int32_t max_nodes = 0;  // largest expression term (0: fused terms only)

@@ -31,6 +31,7 @@ void pw_free(mc_program* p) {
     if (v->d_data) (void)hipFree(v->d_data);
     if (v->d_index) (void)hipFree(v->d_index);
     if (v->d_tiles) (void)hipFree(v->d_tiles);
+    if (v->d_samplers) (void)hipFree(v->d_samplers);
     delete v;
     p->pw = nullptr;
 }
@@ -89,6 +90,8 @@ extern "C" int mc_program_enable_pointwise(mc_program* p) {
     if (e == hipSuccess) e = pw_upload(&v->d_data, p->h_data.data(), (size_t)p->pw_n_data);
     if (e == hipSuccess) e = pw_upload(&v->d_index, p->h_index.data(), (size_t)p->pw_n_index);
     if (e == hipSuccess) e = pw_upload(&v->d_tiles, tiles.data(), tiles.size());
+    if (e == hipSuccess)
+        e = pw_upload(&v->d_samplers, p->pw_samplers.data(), p->pw_samplers.size());
     if (e != hipSuccess) {
         pw_free(p);
         return fail(e == hipErrorOutOfMemory ? MC_ERR_NOMEM : MC_ERR_HIP,

@@ -1,6 +1,7 @@
 // run_predictive.hip — posterior predictive replicates on the pointwise view
-// of a program (csrc/predictive.h): mc_predictive_draw (the scalar definition,
-// host only), mc_predictive_workspace_bytes, mc_predictive.
+// of a program (csrc/predictive.h): mc_predictive_draw and
+// mc_predictive_draw_discrete (the scalar definitions, host only),
+// mc_predictive_workspace_bytes, mc_predictive, mc_predictive_eq.
 #include "host.h"
 #include "predictive.h"
 #include "pw_view.h"
@@ -15,6 +16,7 @@ struct PpPlan {
     const PwView* v;
     int64_t Sp, Np, B, per;
     bool gb;
+    int nmax;  // 0: no count term; 16 / 32: the largest one's node bound
 };
 int pp_plan(const mc_program* p, int64_t C, int64_t S, int64_t thin, PpPlan* out) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
@@ -24,8 +26,14 @@ int pp_plan(const mc_program* p, int64_t C, int64_t S, int64_t thin, PpPlan* out
         return fail(MC_ERR_INVALID, "predictive: C, S and thin must be >= 1");
     if (C > INT64_MAX / S) return fail(MC_ERR_INVALID, "predictive: C * S overflows");
     bool gb = false;
+    int nmax = 0;
     for (size_t t = 0; t < p->pw_terms.size(); ++t) {
         const int dist = p->pw_terms[t].dist;
+        // an expression term whose root is a count node (internal.h PwSampler)
+        if (dist == MC_DIST_EXPR && t < p->pw_samplers.size() && p->pw_samplers[t].kind >= 0) {
+            nmax = std::max(nmax, p->pw_terms[t].expr_n > 16 ? 32 : 16);
+            continue;
+        }
         if (!pp_sampled(dist))
             return fail(MC_ERR_UNSUPPORTED, "predictive: term %zu (%s) has no sampling "
                         "distribution", t, dist == MC_DIST_EXPR ? "an expression term"
@@ -39,11 +47,14 @@ int pp_plan(const mc_program* p, int64_t C, int64_t S, int64_t thin, PpPlan* out
     out->Sp = (S + thin - 1) / thin;
     out->Np = C * out->Sp;
     out->gb = gb;
+    out->nmax = nmax;
     pw_split(out->Np, v->ntiles, &out->B, &out->per);
     return MC_OK;
 }
 int64_t pp_need(const PpPlan& L) {
-    return L.B > 1 ? L.B * PP_COUNT * L.v->M * (int64_t)sizeof(double) : 0;
+    // (the five fields per block; with count terms the ties' count as well)
+    return L.B > 1 ? L.B * (PP_COUNT + (L.nmax > 0 ? 1 : 0)) * L.v->M * (int64_t)sizeof(double)
+                   : 0;
 }
 
 }  // namespace
@@ -59,6 +70,23 @@ extern "C" int mc_predictive_draw(int dist, float loc_or_alpha, float scale_or_r
     return MC_OK;
 }
 
+extern "C" int mc_predictive_draw_discrete(int kind, float total, float eta, uint64_t seed,
+                                           uint32_t chain, uint32_t iter, uint32_t obs,
+                                           float* out) {
+    if (!out) return fail(MC_ERR_INVALID, "predictive: out is NULL");
+    if (kind < MC_DISCRETE_BERNOULLI || kind > MC_DISCRETE_POISSON)
+        return fail(MC_ERR_INVALID, "predictive: unknown discrete distribution %d", kind);
+    *out = pp_draw_discrete(kind, total, eta, seed, chain, iter, obs);
+    return MC_OK;
+}
+
+extern "C" int32_t mc_program_num_count_terms(const mc_program* p) {
+    if (!p) return fail(MC_ERR_INVALID, "program is NULL");
+    int32_t n = 0;
+    for (const PwSampler& sd : p->pw_samplers) n += sd.kind >= 0 ? 1 : 0;
+    return n;
+}
+
 extern "C" int64_t mc_predictive_workspace_bytes(const mc_program* p, int64_t C, int64_t S,
                                                  int64_t thin) {
     PpPlan L;
@@ -70,10 +98,21 @@ extern "C" int mc_predictive(const mc_program* p, int64_t C, int64_t S, int64_t 
                              uint64_t seed, int64_t chain_offset, int64_t iter_offset,
                              const float* samples, double* stats, float* yrep, void* ws,
                              int64_t ws_bytes, void* hip_stream) {
+    return mc_predictive_eq(p, C, S, thin, seed, chain_offset, iter_offset, samples, stats,
+                            nullptr, yrep, ws, ws_bytes, hip_stream);
+}
+
+extern "C" int mc_predictive_eq(const mc_program* p, int64_t C, int64_t S, int64_t thin,
+                                uint64_t seed, int64_t chain_offset, int64_t iter_offset,
+                                const float* samples, double* stats, double* equal, float* yrep,
+                                void* ws, int64_t ws_bytes, void* hip_stream) {
     PpPlan L;
     const int rc = pp_plan(p, C, S, thin, &L);
     if (rc != MC_OK) return rc;
     if (!samples || !stats) return fail(MC_ERR_INVALID, "predictive: NULL samples / stats");
+    if (equal && L.nmax == 0)
+        return fail(MC_ERR_UNSUPPORTED, "predictive: the count of ties needs a likelihood with "
+                    "a count term (pass equal = NULL)");
     if (chain_offset < 0 || chain_offset + C > (int64_t)UINT32_MAX)
         return fail(MC_ERR_INVALID, "predictive: chain ids must fit in 32 bits");
     if (iter_offset < 0 || iter_offset + S > (int64_t)UINT32_MAX)
@@ -95,17 +134,25 @@ extern "C" int mc_predictive(const mc_program* p, int64_t C, int64_t S, int64_t 
     R.iter0 = (uint32_t)iter_offset;
     // one block of draws: its partial is the result
     double* part = L.B > 1 ? (double*)ws : stats;
+    double* eqpart = !equal ? nullptr
+                     : L.B > 1 ? (double*)ws + L.B * PP_COUNT * L.v->M : equal;
     const dim3 grid((unsigned)L.v->ntiles, (unsigned)L.B);
-    if (L.gb)
-        hipLaunchKernelGGL(k_predictive<true>, grid, dim3(kPwBlock), 0, st, X, R, samples, part,
-                           yrep);
-    else
-        hipLaunchKernelGGL(k_predictive<false>, grid, dim3(kPwBlock), 0, st, X, R, samples, part,
-                           yrep);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kPwBlock), 0, st, X, R, samples, part, yrep,
+                           (const PwSampler*)L.v->d_samplers, eqpart);
+    };
+    // programs with count terms run the NMAX > 0 kernel (it carries every
+    // sampler); everything else the kernels without that path
+    const int nmax = L.nmax;
+    if (nmax > 16) launch(k_predictive<true, 32>);
+    else if (nmax > 0) launch(k_predictive<true, 16>);
+    else if (L.gb) launch(k_predictive<true, 0>);
+    else launch(k_predictive<false, 0>);
     MC_HIP_TRY(hipGetLastError());
     if (L.B > 1) {
         hipLaunchKernelGGL(k_pp_merge, dim3((unsigned)((L.v->M + 255) / 256)), dim3(256), 0, st,
-                           (const double*)part, L.v->M, (int32_t)L.B, stats);
+                           (const double*)part, L.v->M, (int32_t)L.B, stats,
+                           (const double*)eqpart, equal);
         MC_HIP_TRY(hipGetLastError());
     }
     return MC_OK;

@@ -562,10 +562,15 @@ def merge_predictive(parts):
     over the finite counts ``n - nonfinite`` (a side without finite replicates
     leaves the other's moments; both without: NaN), the three counts added.
     The device merge (csrc/predictive.h k_pp_merge) and the rank merge apply
-    the same rules."""
+    the same rules.  When every partial carries ``equal`` (the finite
+    replicates equal to the observation: likelihoods with a count term), it is
+    added too; otherwise the result has none."""
     parts = list(parts)
     if not parts:
         raise ValueError("merge_predictive needs at least one partial")
+    equal = None
+    if all("equal" in p for p in parts):
+        equal = sum(np.asarray(p["equal"], np.float64) for p in parts)
     acc = {f: np.array(parts[0][f], dtype=np.float64, copy=True) for f in PP_FIELDS}
     with np.errstate(all="ignore"):
         for p in parts[1:]:
@@ -581,6 +586,8 @@ def merge_predictive(parts):
                    "m2": np.where(keep, acc["m2"], np.where(take, b["m2"], m2)),
                    "below": acc["below"] + b["below"],
                    "nonfinite": acc["nonfinite"] + b["nonfinite"]}
+    if equal is not None:
+        acc["equal"] = np.array(equal, dtype=np.float64, copy=True)
     return acc
 
 
@@ -594,14 +601,16 @@ def posterior_predictive(log_likelihood_fn, samples, layout=None, *, seed=0, thi
     likelihood is one observation.  For every processed draw (iterations 0,
     ``thin``, 2 ``thin``, ... of every chain: S' = ceil(S / thin)) and
     observation, one replicate is drawn from the term's distribution — Normal,
-    HalfNormal, Exponential, Gamma or Beta — with the operand values of that
-    draw.  A replicate is a pure function of (``seed``, chain index +
+    HalfNormal, Exponential, Gamma or Beta, or the count distribution of a
+    ``Bernoulli(logits=)`` / ``Binomial(n, logits=)`` / ``Poisson(log_rate=)``
+    likelihood term — with the operand values of that draw.  A replicate is a pure function of (``seed``, chain index +
     ``chain_offset``, iteration index + ``iter_offset``, observation) and those
     operand values (include/mcmc355.h), so shards of chains or iterations and
     thinned runs reproduce the rows of the whole.  A term's weight (``mx.mean``,
     a tempering factor) is ignored: replicates come from the untempered
-    observation model.  Expression and identity terms have no sampling
-    distribution: ``EngineError`` (MC_ERR_UNSUPPORTED) before any launch.
+    observation model.  Identity terms and every other expression term have no
+    sampling distribution: ``EngineError`` (MC_ERR_UNSUPPORTED) before any
+    launch.
 
     Returns float64 NumPy [M] arrays ``n`` (draws processed), ``mean`` and
     ``m2`` (moments of the finite replicates), ``below`` (finite replicates
@@ -609,7 +618,10 @@ def posterior_predictive(log_likelihood_fn, samples, layout=None, *, seed=0, thi
     (replicates of a draw with an invalid scale, rate or shape: NaN, counted,
     never raised) — a partial ``merge_predictive`` combines with other shards —
     and the derived ``var`` = m2 / (n_finite - 1) and ``pit`` = below /
-    n_finite, n_finite = n - nonfinite.  ``replicates=True`` adds
+    n_finite, n_finite = n - nonfinite.  A likelihood with a count term also
+    returns ``equal`` (finite replicates equal to the observation) and the
+    mid-rank ``pit_mid`` = (below + equal / 2) / n_finite, the PIT of a
+    discrete outcome; ``pit`` stays as it is.  ``replicates=True`` adds
     ``replicates``, the [C, S', M] float32 device tensor (small problems only).
     With an initialised process group (``group=False`` stays local) the ranks'
     partials are gathered and merged in rank order; the replicates stay this
@@ -631,18 +643,25 @@ def posterior_predictive(log_likelihood_fn, samples, layout=None, *, seed=0, thi
         _lib.check(int(nb))
     Sp = (S + thin - 1) // thin
     st = torch.empty((_lib.MC_PP_COUNT, M), dtype=torch.float64, device=x.device)
+    eq = (torch.empty(M, dtype=torch.float64, device=x.device)
+          if lib.mc_program_num_count_terms(prog.handle) > 0 else None)
     rep = torch.empty((C, Sp, M), dtype=torch.float32, device=x.device) if replicates else None
     ws = torch.empty(max(int(nb), 1), dtype=torch.uint8, device=x.device)
-    _lib.check(lib.mc_predictive(prog.handle, C, S, thin, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                 int(chain_offset), int(iter_offset), _lib.ptr(x), _lib.ptr(st),
-                                 _lib.ptr(rep), _lib.ptr(ws), nb, _lib.stream_handle()))
+    _lib.check(lib.mc_predictive_eq(prog.handle, C, S, thin, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                    int(chain_offset), int(iter_offset), _lib.ptr(x),
+                                    _lib.ptr(st), _lib.ptr(eq), _lib.ptr(rep), _lib.ptr(ws), nb,
+                                    _lib.stream_handle()))
     host = st.cpu().numpy()   # (synchronises: prog, x and ws outlive the launch)
     part = {f: host[k].copy() for k, f in enumerate(PP_FIELDS)}
+    if eq is not None:
+        part["equal"] = eq.cpu().numpy()
     out = merge_predictive(_gather_parts(part, group))
     with np.errstate(all="ignore"):
         nfin = out["n"] - out["nonfinite"]
         out["var"] = out["m2"] / (nfin - 1.0)
         out["pit"] = out["below"] / nfin
+        if "equal" in out:
+            out["pit_mid"] = (out["below"] + 0.5 * out["equal"]) / nfin
     if replicates:
         out["replicates"] = rep
     return out

@@ -1,5 +1,6 @@
 """Distributions of the tape: ``Distribution``, ``Normal``, ``HalfNormal``,
-``Exponential``, ``Gamma``, ``Beta``.
+``Exponential``, ``Gamma``, ``Beta``, and the count likelihoods ``Bernoulli``,
+``Binomial``, ``Poisson``.
 
 Same constructor arguments, ``log_prob(value)`` / ``sample(key, shape)``
 contract and formulas as the reference (mlx_mcmc/distributions/base.py:6-54,
@@ -16,6 +17,16 @@ beta.py:8-151):
                for 0 < x < 1, -inf otherwise
   (the gammaln normalisers are values without gradient, as the reference's
   host scipy gammaln)
+
+The count likelihoods (not in the reference) are log masses of observed data
+under a traced logit / log rate, with softplus(x) = max(x, 0) + log1p(exp(-|x|)):
+
+  Bernoulli(logits=eta):   log p(y) = -softplus(eta) if y = 0, -softplus(-eta) if y = 1
+  Binomial(n, logits=eta): log p(y) = log C(n, y) + y eta - n softplus(eta), y = 0 .. n
+  Poisson(log_rate=theta): log p(y) = y theta - exp(theta) - log y!, y = 0, 1, ...
+  (-inf outside the support; ``probs=`` / ``rate=`` go through eta = logit p /
+  theta = log r and give -inf for p outside (0, 1) / r <= 0; the value and
+  total_count are data, never traced)
 
 Inside a traced ``log_prob(params)`` (any argument is a traced parameter),
 ``log_prob`` records a fused term for the HIP tape (see _trace.py).  On
@@ -251,4 +262,185 @@ class Beta(Distribution):
         return f"Beta(alpha={_scalar_repr(self.alpha)}, beta={_scalar_repr(self.beta)})"
 
 
-__all__ = ["Distribution", "Normal", "HalfNormal", "Exponential", "Gamma", "Beta", "Key"]
+def _gpu_discrete_log_prob(kind: int, name: str, value, total, eta) -> np.ndarray:
+    """The count node's value on concrete arguments (mc_discrete_log_prob) plus
+    the f32 normaliser, added in f32 as the traced ADD node adds it."""
+    import torch
+
+    dev = _lib.require_device()
+    v, e = _to_f32(value), _to_f32(eta)
+    t = _to_f32(total) if total is not None else None
+    shapes = [a.shape for a in (v, t, e) if a is not None]
+    out_shape = np.broadcast_shapes(*shapes)
+    n = int(np.prod(out_shape)) if out_shape else 1
+
+    def dev_arr(a):
+        if a is None:
+            return None, 1
+        if a.size == 1:
+            return torch.from_numpy(a.reshape(1).copy()).to(dev), 1
+        return torch.from_numpy(np.broadcast_to(a, out_shape).reshape(-1).copy()).to(dev), 0
+
+    tv, bv = dev_arr(v)
+    tt, bt = dev_arr(t)
+    te, be = dev_arr(e)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().mc_discrete_log_prob(kind, n, _lib.ptr(tv), bv, _lib.ptr(tt), bt,
+                                                _lib.ptr(te), be, _lib.ptr(out),
+                                                _lib.stream_handle()))
+    core = out.cpu().numpy().reshape(out_shape)
+    if name == "Bernoulli":
+        return core
+    norm = np.broadcast_to(_trace.discrete_norm(name, v, t), out_shape)
+    return (core + norm).astype(np.float32)
+
+
+def _one_of(name: str, **kw):
+    """Exactly one parameterisation: (its keyword, its value)."""
+    given = [(k, v) for k, v in kw.items() if v is not None]
+    if len(given) != 1:
+        raise ValueError(f"{name} takes exactly one of " + " / ".join(f"{k}=" for k in kw)
+                         + f" (got {len(given)})")
+    return given[0]
+
+
+def _logit64(p):
+    p = np.asarray(_to_f32(p), np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.log(p) - np.log1p(-p)
+
+
+def _sigmoid64(x):
+    x = np.asarray(_to_f32(x), np.float64)
+    with np.errstate(over="ignore"):
+        return np.where(x >= 0, 1.0 / (1.0 + np.exp(-x)), np.exp(x) / (1.0 + np.exp(x)))
+
+
+class _Discrete(Distribution):
+    """A count likelihood: one natural argument (logit / log rate) or its
+    probability / rate form; log_prob's value (and total_count) are data."""
+
+    _name = ""
+    _kind = -1
+    _natural = ""
+
+    def _total(self):
+        return None
+
+    def log_prob(self, value):
+        key, arg = self._param
+        natural = key == self._natural
+        total = self._total()
+        if _trace.is_symbolic(value, total, arg):
+            return _trace.discrete_expr(self._name, value, total, arg, natural)
+        if natural:
+            eta = _to_f32(arg)
+        else:
+            # the lowering's f32 operations: log p - log1p(-p), log r; outside
+            # the parameter's domain -inf
+            p = _to_f32(arg)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                if self._name == "Poisson":
+                    eta = np.log(p)
+                    ok = p > 0
+                else:
+                    eta = (np.log(p) - np.log1p(-p)).astype(np.float32)
+                    ok = (p > 0) & (p < 1)
+            eta = np.where(ok, eta, np.float32(0)).astype(np.float32)
+        out = _gpu_discrete_log_prob(self._kind, self._name, value, total, eta)
+        if not natural:
+            out = np.where(np.broadcast_to(ok, out.shape), out, -np.inf).astype(np.float32)
+        return out
+
+
+class Bernoulli(_Discrete):
+    """Bernoulli(probs=None, logits=None): y in {0, 1}."""
+
+    _name, _kind, _natural = "Bernoulli", _lib.MC_DISCRETE_BERNOULLI, "logits"
+
+    def __init__(self, probs=None, logits=None):
+        self._param = _one_of("Bernoulli", probs=probs, logits=logits)
+        self.probs, self.logits = probs, logits
+
+    def _p(self):
+        return _sigmoid64(self.logits) if self.probs is None else np.asarray(
+            _to_f32(self.probs), np.float64)
+
+    def sample(self, key, shape=()):
+        return _host_rng(key).binomial(1, self._p(), size=shape or None).astype(np.float32)
+
+    def mean(self):
+        return self._p().astype(np.float32)
+
+    def variance(self):
+        p = self._p()
+        return (p * (1 - p)).astype(np.float32)
+
+    def __repr__(self):
+        k, v = self._param
+        return f"Bernoulli({k}={_scalar_repr(v)})"
+
+
+class Binomial(_Discrete):
+    """Binomial(total_count, probs=None, logits=None): y in {0 .. total_count}."""
+
+    _name, _kind, _natural = "Binomial", _lib.MC_DISCRETE_BINOMIAL, "logits"
+
+    def __init__(self, total_count, probs=None, logits=None):
+        self._param = _one_of("Binomial", probs=probs, logits=logits)
+        self.total_count, self.probs, self.logits = total_count, probs, logits
+
+    def _total(self):
+        return self.total_count
+
+    def _p(self):
+        return _sigmoid64(self.logits) if self.probs is None else np.asarray(
+            _to_f32(self.probs), np.float64)
+
+    def sample(self, key, shape=()):
+        n = np.asarray(_to_f32(self.total_count)).astype(np.int64)
+        return _host_rng(key).binomial(n, self._p(), size=shape or None).astype(np.float32)
+
+    def mean(self):
+        return (_to_f32(self.total_count) * self._p()).astype(np.float32)
+
+    def variance(self):
+        p = self._p()
+        return (_to_f32(self.total_count) * p * (1 - p)).astype(np.float32)
+
+    def __repr__(self):
+        k, v = self._param
+        return f"Binomial(total_count={_scalar_repr(self.total_count)}, {k}={_scalar_repr(v)})"
+
+
+class Poisson(_Discrete):
+    """Poisson(rate=None, log_rate=None): y in {0, 1, ...}."""
+
+    _name, _kind, _natural = "Poisson", _lib.MC_DISCRETE_POISSON, "log_rate"
+
+    def __init__(self, rate=None, log_rate=None):
+        self._param = _one_of("Poisson", rate=rate, log_rate=log_rate)
+        self.rate, self.log_rate = rate, log_rate
+
+    def _rate(self):
+        if self.rate is not None:
+            return np.asarray(_to_f32(self.rate), np.float64)
+        with np.errstate(over="ignore"):
+            return np.exp(np.asarray(_to_f32(self.log_rate), np.float64))
+
+    def sample(self, key, shape=()):
+        return _host_rng(key).poisson(self._rate(), size=shape or None).astype(np.float32)
+
+    def mean(self):
+        return self._rate().astype(np.float32)
+
+    def variance(self):
+        return self._rate().astype(np.float32)
+
+    def __repr__(self):
+        k, v = self._param
+        return f"Poisson({k}={_scalar_repr(v)})"
+
+
+__all__ = ["Distribution", "Normal", "HalfNormal", "Exponential", "Gamma", "Beta", "Bernoulli",
+           "Binomial", "Poisson", "Key"]
