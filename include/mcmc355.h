@@ -319,6 +319,17 @@ int32_t mc_program_lanes_fast(const mc_program* prog);
 int32_t mc_program_lane_slots(const mc_program* prog);
 int32_t mc_program_lane_rep(const mc_program* prog);
 int32_t mc_program_lane_bundle(const mc_program* prog);
+/* 1 when HMC launches of the program take the dense route: a fast-form
+ * hierarchical program under automatic slicing runs a chain pair per
+ * workgroup (k_hmc_lf reads no observation per step, so the pair's slices are
+ * the waves of one workgroup exchanging through LDS, or one wave without an
+ * exchange), on a plan of its own beside the program's; *slices its slices
+ * (waves per chain pair: 1, 4 or 8) and *slots its register slots per lane
+ * (either may be NULL).  0 (and zeros) when HMC runs the program-level plan:
+ * an explicit slice count, another form, MC_LANES_FAST=0 / MC_LANES_FORM=0.
+ * NUTS, MH and the pointwise kernels always run the program-level plan.
+ * -1 on a null program.                                                     */
+int32_t mc_program_hmc_dense(const mc_program* prog, int32_t* slices, int32_t* slots);
 /* Why the program's HMC launches do not run the lane-resident kernel (e.g.
  * "lane-resident kernel: more than 4 broadcast parameters"), or "" when they
  * do or no plan was attempted; valid until the next set_slices /
@@ -534,6 +545,14 @@ int mc_debug_lane_plan_host(mc_program* prog, int32_t num_slices);
  * slice planner refuses; the lane digests 0 and MC_ERR_UNSUPPORTED (the reason
  * in mc_last_error) when only the lane planner declines.                    */
 int mc_debug_plan_digest(mc_program* prog, int32_t num_slices, uint64_t* out, int32_t n_out);
+/* Test hook (host table, also of a host-only program after
+ * mc_debug_lane_plan_host): the lane plan's moment constants, four floats
+ * (c, R, Q, n) per [slice][4 slots][64 lanes]: of the run of the first swept
+ * term that (slot, lane) holds, its centre c = (float) mean, R = sum (x - c),
+ * Q = sum (x - c)^2 (float64 sums in element order, rounded once) and element
+ * count; zeros for an empty run.  Not among the digests above (derived from
+ * `data`).  Returns the number of floats (out may be NULL), negative on error. */
+int64_t mc_debug_lane_moments(const mc_program* prog, float* out, int64_t n_out);
 int64_t mc_debug_expr_jit_lane_source(const mc_program* prog, char* buf, int64_t cap);
 /* Test hook (host tables, also of a host-only program): the tape plan of term
  * `term` in evaluation order (wave tasks last, csrc/program.hip), ten values,

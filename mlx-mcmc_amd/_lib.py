@@ -226,6 +226,7 @@ SIGNATURES = [
     ("mc_program_lanes_fast", ctypes.c_int32, [_VP]),
     ("mc_program_lane_slots", ctypes.c_int32, [_VP]),
     ("mc_program_lane_rep", ctypes.c_int32, [_VP]),
+    ("mc_program_hmc_dense", ctypes.c_int32, [_VP, _VP, _VP]),
     ("mc_program_lane_bundle", ctypes.c_int32, [_VP]),
     ("mc_program_kernel_note", ctypes.c_char_p, [_VP]),
     ("mc_program_nuts_lanes", ctypes.c_int32, [_VP, ctypes.c_int32]),
@@ -261,6 +262,8 @@ SIGNATURES = [
     ("mc_debug_lane_plan_host", ctypes.c_int, [_VP, ctypes.c_int32]),
     ("mc_debug_plan_digest", ctypes.c_int,
      [_VP, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
+    ("mc_debug_lane_moments", ctypes.c_int64,
+     [_VP, ctypes.POINTER(ctypes.c_float), ctypes.c_int64]),
     ("mc_debug_expr_jit_lane_source", ctypes.c_int64, [_VP, ctypes.c_char_p, ctypes.c_int64]),
     ("mc_debug_term_plan", ctypes.c_int,
      [_VP, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),

@@ -1463,6 +1463,15 @@ class Program:
         return int(_lib.load().mc_program_lane_rep(self.handle))
 
     @property
+    def hmc_dense(self):
+        """(slices, slots) of the dense HMC route — a chain pair per workgroup,
+        `slices` waves of `slots` register slots per lane (mc_program_hmc_dense)
+        — or None when HMC launches run the program-level plan."""
+        s, r = ctypes.c_int32(0), ctypes.c_int32(0)
+        on = _lib.load().mc_program_hmc_dense(self.handle, ctypes.byref(s), ctypes.byref(r))
+        return (int(s.value), int(r.value)) if on == 1 else None
+
+    @property
     def lane_bundle(self) -> int:
         """Widest bundle of private parameters one element of a gathered
         expression term reads on the lane-resident plan (alpha[g] + beta[g] * x:

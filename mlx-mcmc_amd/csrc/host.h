@@ -116,6 +116,12 @@ struct LanePlan {
     int rep = 1;         // lanes per private parameter (lanes.h LrCtx::rep)
     std::vector<int32_t> rng;  // [S][64][4] lane RNG plan (lanes_fast.h lf_rng_*), or empty
     int32_t* d_rng = nullptr;
+    // [S][kLrMaxSlots][64][4]: per run of the first swept term its centre c,
+    // centred sums R and Q and element count n (plan_lanes.hip lane_moments;
+    // lanes_fast.h lf_moments).  Derived from `data`: not among the digests.
+    std::vector<float> mom;
+    float* d_mom = nullptr;
+    int rep_cap = 0;     // > 0: the planner keeps rep <= rep_cap (the dense HMC plan: 1)
     int has_xf = 0;      // a shared parameter is transformed, or an identity term
                          // (no NUTS lanes, no term interpreter)
     int has_expr = 0;    // LS_EXPR terms: only the JIT-compiled k_hmc_lr runs the plan
@@ -165,6 +171,11 @@ struct mc_program {
     std::vector<int32_t> h_index;
     SlicePlan sl;
     LanePlan lr;
+    // the dense HMC plan (program.hip plan_hmc_dense): the fast-form program at
+    // one lane per parameter, a chain pair per workgroup (lanes_fast.h DN): one
+    // slice, or 4 / 8 at two register slots.  Beside the program's plan, which
+    // NUTS, MH and the pointwise kernels keep; only under automatic slicing.
+    LanePlan lrd;
     int32_t slice_kernel = 0;  // 0 automatic, 1 term interpreter, 2 lane-resident
     // why the automatic plan did not reach the lane-resident kernel ("" when it
     // did or was not asked to): mc_program_kernel_note
@@ -377,10 +388,9 @@ inline bool interp_ok(const mc_program* p) {
     return !has_transform(p) && !has_affine(p) && !has_expr(p);
 }
 
-inline LrCtx lrctx_of(const mc_program* p) {
+inline LrCtx lrctx_of(const mc_program* p, const LanePlan& L) {
     LrCtx c;
     std::memset(&c, 0, sizeof(c));
-    const LanePlan& L = p->lr;
     c.terms = L.d_terms;
     c.data = L.d_data;
     c.blocks = L.d_blocks;
@@ -403,8 +413,10 @@ inline LrCtx lrctx_of(const mc_program* p) {
     c.has_xf = L.has_xf;
     c.rep = L.rep;
     c.rng = (const int4*)L.d_rng;
+    c.mom = (const float4*)L.d_mom;
     return c;
 }
+inline LrCtx lrctx_of(const mc_program* p) { return lrctx_of(p, p->lr); }
 // ---------------------------------------------------------------------------
 // geometry helpers
 // ---------------------------------------------------------------------------
@@ -713,6 +725,14 @@ inline bool ws_reserve(const void* ws, uint64_t need, uint64_t bytes, uint32_t* 
 
 
 
+// HMC launches of the program take the dense route (mc_program::lrd)
+inline bool lanes_fast_enabled();
+inline bool lanes_forms_enabled();
+inline bool hmc_dense_route(const mc_program* p) {
+    return p->lrd.ok && p->lr.ok && p->slice_kernel != 1 && lanes_fast_enabled() &&
+           lanes_forms_enabled();
+}
+
 // the fast-form kernel (lanes_fast.h) for programs that qualify, unless
 // MC_LANES_FAST=0 in the environment (A/B timing against k_hmc_lr)
 inline int g_lanes_fast = -1;  // mc_debug_lanes_fast; -1: MC_LANES_FAST from the environment
@@ -762,4 +782,11 @@ int hmc_lanes_rs1(const mc_program*, const mc_run_config*, void*, float*, const 
 int hmc_lanes_rs2(const mc_program*, const mc_run_config*, void*, float*, const mc_trace*, void*,
                   hipStream_t);
 int hmc_lanes_rs4(const mc_program*, const mc_run_config*, void*, float*, const mc_trace*, void*,
+                  hipStream_t);
+// ... and the dense launches (run_lanes.h launch_hmc_dense)
+int hmc_dense_rs1(const mc_program*, const mc_run_config*, void*, float*, const mc_trace*, void*,
+                  hipStream_t);
+int hmc_dense_rs2(const mc_program*, const mc_run_config*, void*, float*, const mc_trace*, void*,
+                  hipStream_t);
+int hmc_dense_rs4(const mc_program*, const mc_run_config*, void*, float*, const mc_trace*, void*,
                   hipStream_t);

@@ -140,6 +140,9 @@ struct LrCtx {
                                  // over the raw parameter (its log-Jacobian)
     int32_t has_xf;              // a transform or an identity term (k_hmc_lf)
     const int4* rng;             // [S][64] lane RNG plan (lf_rng_*), or nullptr
+    const float4* mom;           // [S][kLrMaxSlots][64]: the moment constants
+                                 // (c, R, Q, n) of the swept term's run of (slot,
+                                 // lane) (plan_lanes.hip lane_moments; k_hmc_lf)
     int32_t rep;                 // lanes per private parameter (1, 2, 4, 8 or 16):
                                  // a parameter's elements are split over the
                                  // `rep` lanes of its group (lanes j & ~(rep-1)

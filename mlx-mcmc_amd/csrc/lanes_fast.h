@@ -26,16 +26,16 @@
 //   * both chains' per-step arithmetic runs packed (v_pk_*_f32: the same
 //     IEEE operations per chain, two chains per instruction), the per-launch
 //     uniform values pinned in VGPRs (no SGPR spills reloaded per step);
-//   * the moment sweep sums the second moment alone, even and odd elements in
-//     separate packed accumulators (two dependency chains; a dependent
-//     v_pk_fma_f32 advances every 10 cycles, scripts/micro/pk_probe.hip): per
-//     element and chain pair d = x - th and one fma.  The first moment
-//     sum (x - th) is linear in th: about a centre c it is
-//     sum (x - c) + n (c - th), and the data's share — c, the run's mean, and
-//     R = sum (x - c) — is formed once per launch (lf_run_consts: float64 sums
-//     in element order, rounded once), so a step forms M1 = fma(n, c - th, R)
-//     (lf_m1) instead of adding every element again: a regrouping of the same
-//     sum, with three roundings where the serial sum had one per element;
+//   * no step reads an observation: both moment sums of a run are closed
+//     forms in the position about the run's centre c — sum (x - th) =
+//     R + n (c - th), sum (x - th)^2 = Q + 2 (c - th) R + n (c - th)^2 — and
+//     the data's share (c, R = sum (x - c), Q = sum (x - c)^2, n) is a table
+//     the planner forms once per program (plan_lanes.hip lane_moments: float64
+//     sums in element order, rounded once; lf_moments below): a regrouping of
+//     the same sums, with a handful of roundings where a serial sum has one
+//     per element, so the slice block is neither copied to LDS nor read;
+//   * with nothing to sweep, a chain pair's slices need not be workgroups:
+//     the dense launch (DN below) runs them as the waves of one workgroup;
 //   * the wave totals of the record are reduce-scattered (permlane32 /
 //     permlane16 swaps + one 16-lane DPP row sum) so that pair P's total is
 //     in row perm[P % 4] of register P / 4 — no readlanes, no publish select;
@@ -146,278 +146,26 @@ MC_DEV void lf_rs8(const float (&v)[8], float (&x)[2]) {
     }
 }
 
-// (xy.y, xy.y) - th in one v_pk_add_f32: the backend copies the odd register
-// of a pair to an even one before broadcasting it (one v_mov per element
-// pair); op_sel on the pair reads it in place.
-MC_DEV f2 lf_hi_minus(f2 xy, f2 th) {
-    f2 d;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]"
-        : "=v"(d)
-        : "v"(xy), "v"(th));
-    return d;
-}
-
-// The data's share of a run's first moment, once per launch: the sweep's
-// M1 = sum_e (x_e - th) is linear in th, and regrouped about a centre c it is
-// sum_e (x_e - c) + n (c - th) = R + n (c - th): R and c depend on the run's
-// observations alone.  c = (float) mean(x), R = (float) sum_e (x_e - c), both
-// sums in double and in element order (group g of the run is the float4 at
-// xv + 256 g; the tile is padded to whole groups, so every load is in bounds);
-// an empty run has c = R = 0.  Returns (c, R).  Centred, because
-// sum x - n th would cancel at the observations' magnitude; this form
-// carries three roundings (c - th, the fma, R) where the serial sum carried
-// one per element.
-MC_DEV f2 lf_run_consts(const float* xv, int len) {
-    const int ng = (len + 3) >> 2;
-    auto total = [&](double c) {
-        double s = 0.0;
-#pragma unroll 4
-        for (int g = 0; g < ng; ++g) {
-            const float4 a = *(const float4*)(xv + g * 256);
-            const float x[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (4 * g + k < len) s += (double)x[k] - c;
-        }
-        return s;
-    };
-    if (len <= 0) return (f2){0.f, 0.f};
-    const float c = (float)(total(0.0) / (double)len);
-    return (f2){c, (float)total((double)c)};
-}
-
-// M1 of a run from its launch constants c and R (lf_run_consts), its element
-// count cnt (both chains) and the position th: fma(cnt, c - th, R), per
-// chain.  Not packed: c and R are one register each, and packed operands
-// would want them broadcast in aligned register pairs kept for the whole
-// launch — two registers more than the kernel of the Large shape has without
-// spilling; the two chains' subtract and fma are four instructions a step.
-MC_DEV f2 lf_m1(f2 cnt, float c, float R, f2 th) {
-    return (f2){__builtin_fmaf(cnt[0], c - th[0], R), __builtin_fmaf(cnt[1], c - th[1], R)};
-}
-
-// Second-moment sum of one lane's run (value = data x, loc = the lane's
-// private parameter th) for both chains, packed FP32: d = x - th,
-// s2 = fma(d, d, s2), with the even and odd elements in separate packed
-// accumulators (two independent dependency chains).  (The first moment needs
-// no sweep: lf_m1.)
-// REREAD (one register slot, where the bounds are in SGPRs): the uniform
-// bounds are opaque per sweep, so the trip conditions derived from them are
-// scalar compares at their use (SCC), not per-launch lane masks that occupy
-// SGPR pairs and spill (a v_readlane per use in the step loop).
-template <bool REREAD = false>
-MC_DEV void lf_moments(const float* xv, int len, int lmin4, int lmax, f2 th, f2& s2) {
-    if constexpr (REREAD) asm volatile("" : "+s"(lmin4), "+s"(lmax));
-    f2 a2[2];
-    // a register pair's elements broadcast by swizzle (op_sel on the pair,
-    // no copy of the odd register); the first pair assigns the accumulators
-    // (d * d: what fma(d, d, 0) rounds to), so no zeros are materialised per
-    // sweep
-    auto pair = [&](f2 xy, auto first) {
-        const f2 d0 = xy.xx - th;
-        const f2 d1 = lf_hi_minus(xy, th);
-        if constexpr (decltype(first)::value) {
-            a2[0] = d0 * d0;
-            a2[1] = d1 * d1;
-        } else {
-            a2[0] = pk_fma(d0, d0, a2[0]);
-            a2[1] = pk_fma(d1, d1, a2[1]);
-        }
-    };
-    const std::false_type acc;
-    int u4 = 0;
-    // 16 elements per round over two register sets that alternate (no
-    // copies), each round's loads written ahead of the round before it.  As
-    // compiled (scripts/isa_sweep.py, profiles/lf_sweep_pipeline/isa_parent.txt)
-    // only every second round's loads stay there: the register allocator
-    // gives set A's registers to round(B)'s temporaries, so A's loads are
-    // issued after round(B) and waited for at once.  lf_moments_pre pins the
-    // order; this form is kept where runs are a round or none long.
-    if (lmin4 >= 4) {
-        float4 A[4], B[4];
-        auto load = [&](float4 (&X)[4], int g) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) X[q] = *(const float4*)(xv + (g + q) * 256);
-        };
-        auto round = [&](const float4 (&X)[4], auto first) {
-            pair((f2){X[0].x, X[0].y}, first);
-            pair((f2){X[0].z, X[0].w}, acc);
-#pragma unroll
-            for (int q = 1; q < 4; ++q) {
-                pair((f2){X[q].x, X[q].y}, acc);
-                pair((f2){X[q].z, X[q].w}, acc);
-            }
-        };
-        // (the prefetch index is clamped to the last full round: the loads
-        // are unconditional, so the register sets never need copies)
-        const int last = lmin4 - 4;
-        load(A, 0);
-        const bool more = 8 <= lmin4;
-        load(B, min(4, last));
-        round(A, std::true_type());
-        u4 = 4;
-        if (more) {
-            for (;;) {
-                const bool more_a = u4 + 8 <= lmin4;
-                load(A, min(u4 + 4, last));
-                round(B, acc);
-                u4 += 4;
-                if (!more_a) break;
-                const bool more_b = u4 + 8 <= lmin4;
-                load(B, min(u4 + 4, last));
-                round(A, acc);
-                u4 += 4;
-                if (!more_b) break;
-            }
-        }
-    } else {
-        a2[0] = a2[1] = (f2){0.f, 0.f};
-    }
-    // the groups every lane holds in full (uniform), then the ragged end:
-    // element e of the lanes with more elements (e < lmax, uniform bounds),
-    // masked per lane (the tile is padded to whole groups, so every load is
-    // in bounds); no exec-masked loop, no per-lane branch
-    for (; u4 < lmin4; ++u4) {
-        const float4 a = *(const float4*)(xv + u4 * 256);
-        pair((f2){a.x, a.y}, acc);
-        pair((f2){a.z, a.w}, acc);
-    }
-    const f2 z = {0.f, 0.f};
-    for (int e = 4 * lmin4; e < lmax; e += 4) {
-        const float4 a = *(const float4*)(xv + (e >> 2) * 256);
-        const float x[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (e + k >= lmax) break;  // (uniform)
-            f2 d = (f2){x[k], x[k]} - th;
-            d = (e + k < len) ? d : z;
-            a2[k & 1] = pk_fma(d, d, a2[k & 1]);
-        }
-    }
-    s2 = a2[0] + a2[1];
-}
-
-// The first two rounds' elements of a lane's run (lf_moments): register sets A
-// (groups 0-3) and B (groups 4-7, or the last full round's where there is
-// only one).  Their addresses depend on the run alone, not on the position,
-// so a step issues them ahead of the work that precedes its sweep
-// (lf_issue) and the sweep's first round finds them landed.
-struct LfPre {
-    float4 A[4], B[4];
+// The moment sums of a run at the position th, from the run's constants
+// (plan_lanes.hip lane_moments: LrCtx::mom, one float4 (c, R, Q, n) per slot
+// and lane): about the centre c = (float) mean(x), with R = sum_e (x_e - c)
+// and Q = sum_e (x_e - c)^2 (float64 sums in element order, rounded once) and
+// d = c - th,
+//   M1 = sum_e (x_e - th)   = R + n d           = fma(n, d, R)
+//   M2 = sum_e (x_e - th)^2 = Q + 2 d R + n d^2 = fma(fma(n, d, 2 R), d, Q)
+// exactly, so a step reads no observation: the constants depend on the data
+// alone.  Both chains packed; the roundings are d, the fmas, and the
+// constants' own.  Q and n d^2 are not negative and R is the small residual of
+// the centring, so nothing cancels.  Non-finite or overflowing observations
+// give non-finite constants and a non-finite log p (the proposal is rejected);
+// bit equality with an element-by-element sum is not promised there.
+struct LfMom {
+    f2 c, R, R2, Q, n;  // (each a value broadcast to both chains; R2 = 2 R)
 };
-
-MC_DEV void lf_load4(float4 (&X)[4], const float* xv, int g) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) X[q] = *(const float4*)(xv + (g + q) * 256);
-}
-
-// Issue the loads of LfPre.  Every lane loads, a lane without elements too
-// (its xv is in the tile); a run without a full round loads nothing.  The
-// scheduling barrier keeps the loads here: ahead of what the caller does next.
-template <bool REREAD = false>
-MC_DEV void lf_issue(const float* xv, int lmin4, LfPre& P) {
-    if constexpr (REREAD) asm volatile("" : "+s"(lmin4));
-    if (lmin4 >= 4) {
-        lf_load4(P.A, xv, 0);
-        lf_load4(P.B, xv, min(4, lmin4 - 4));
-    }
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-// lf_moments with the rounds' schedule pinned: the same sums in the same
-// order (the same bits).  P: the run's first two rounds, issued by lf_issue
-// (by the caller, as early as it can).
-//
-// The schedule as compiled (scripts/isa_sweep.py prints it;
-// profiles/lf_first_moment/isa_result.txt): a round is 16 elements, four
-// ds_read_b128 and 32 packed instructions (48 while the sweep summed the
-// first moment too).  A scheduling barrier after each prefetch pins the
-// order — loads of round k + 1, the 32 instructions of round k, loads of
-// round k + 2 ... — while the compiler still counts the waits (lgkmcnt)
-// itself: the wait for a set comes a whole round after its issue (33-34
-// VALU), and round 0's a step's fixed work after it.  (A third register set,
-// loads two rounds ahead, did not fit: 255 VGPRs and 96 bytes of scratch.)
-template <bool REREAD = false>
-MC_DEV void lf_moments_pre(const float* xv, int len, int lmin4, int lmax, f2 th, LfPre& P,
-                           f2& s2) {
-    if constexpr (REREAD) asm volatile("" : "+s"(lmin4), "+s"(lmax));
-    f2 a2[2];
-    // a register pair's elements broadcast by swizzle (op_sel on the pair,
-    // no copy of the odd register); the first pair assigns the accumulators
-    // (d * d: what fma(d, d, 0) rounds to), so no zeros are materialised per
-    // sweep
-    auto pair = [&](f2 xy, auto first) {
-        const f2 d0 = xy.xx - th;
-        const f2 d1 = lf_hi_minus(xy, th);
-        if constexpr (decltype(first)::value) {
-            a2[0] = d0 * d0;
-            a2[1] = d1 * d1;
-        } else {
-            a2[0] = pk_fma(d0, d0, a2[0]);
-            a2[1] = pk_fma(d1, d1, a2[1]);
-        }
-    };
-    const std::false_type acc;
-    int u4 = 0;
-    // 16 elements per round over two register sets that alternate (no copies).
-    // The trip count is derived once: nr full rounds; round 0 (set A) and
-    // round 1 (set B) are in flight on entry, a loop trip computes rounds
-    // k (B) and k + 1 (A) and prefetches rounds k + 1 and k + 2 — the second
-    // clamped to the last full round where the run has none (the loads are
-    // unconditional, so the sets never need copies) — and an odd last round
-    // is computed from set B without a prefetch.
-    if (lmin4 >= 4) {
-        float4(&A)[4] = P.A;
-        float4(&B)[4] = P.B;
-        auto round = [&](const float4 (&X)[4], auto first) {
-            pair((f2){X[0].x, X[0].y}, first);
-            pair((f2){X[0].z, X[0].w}, acc);
-#pragma unroll
-            for (int q = 1; q < 4; ++q) {
-                pair((f2){X[q].x, X[q].y}, acc);
-                pair((f2){X[q].z, X[q].w}, acc);
-            }
-        };
-        const int last = lmin4 - 4;
-        int n = (lmin4 >> 2) - 1;  // rounds after round 0
-        u4 = 4 * (n + 1);
-        round(A, std::true_type());
-        const float* xg = xv + 8 * 256;  // the next prefetch: round 2
-        for (; n >= 2; n -= 2) {
-            lf_load4(A, xg, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            round(B, acc);
-            lf_load4(B, n >= 3 ? xg + 4 * 256 : xv + last * 256, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            round(A, acc);
-            xg += 8 * 256;
-        }
-        if (n == 1) round(B, acc);
-    } else {
-        a2[0] = a2[1] = (f2){0.f, 0.f};
-    }
-    // the groups every lane holds in full (uniform), then the ragged end:
-    // element e of the lanes with more elements (e < lmax, uniform bounds),
-    // masked per lane (the tile is padded to whole groups, so every load is
-    // in bounds); no exec-masked loop, no per-lane branch
-    for (; u4 < lmin4; ++u4) {
-        const float4 a = *(const float4*)(xv + u4 * 256);
-        pair((f2){a.x, a.y}, acc);
-        pair((f2){a.z, a.w}, acc);
-    }
-    const f2 z = {0.f, 0.f};
-    for (int e = 4 * lmin4; e < lmax; e += 4) {
-        const float4 a = *(const float4*)(xv + (e >> 2) * 256);
-        const float x[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (e + k >= lmax) break;  // (uniform)
-            f2 d = (f2){x[k], x[k]} - th;
-            d = (e + k < len) ? d : z;
-            a2[k & 1] = pk_fma(d, d, a2[k & 1]);
-        }
-    }
-    s2 = a2[0] + a2[1];
+MC_DEV void lf_moments(const LfMom& m, f2 th, f2& M1, f2& M2) {
+    const f2 d = m.c - th;
+    M1 = pk_fma(m.n, d, m.R);
+    M2 = pk_fma(pk_fma(m.n, d, m.R2), d, m.Q);
 }
 
 // The fast-form terms of a slice, read once per launch: at most one swept
@@ -469,7 +217,14 @@ MC_DEV LfTerms lf_terms(const MC_CONST LrTerm* tt, int nsweep, int ndirect) {
 // SPEC: launch constants the host resolved (LFS_* bits): their uniform
 // branches, live masks and scalar registers are compiled out; 0 reads them
 // all at run time.  (The own prior's kind needs no such bit: see o_m below.)
-template <int RS, int NSH, int NW, bool X1, int FORM, bool XL = false, int SPEC = 0>
+// DN > 0 — the dense launch (run_lanes.h launch_hmc_dense): a workgroup is one
+// chain pair and its wave w is slice w of DN = NW slices (the plan's S).  The
+// records are exchanged through LDS — a line of 16 floats per (parity, slice),
+// one workgroup barrier per step — so there are no tags, spins, timeout,
+// workspace or co-residency requirement: every wave of the block runs the
+// same steps and iterations (dead chains are clamped, not skipped) and the
+// kernel has no early return, so every barrier is reached by all waves.
+template <int RS, int NSH, int NW, bool X1, int FORM, bool XL = false, int SPEC = 0, int DN = 0>
 __global__ void __launch_bounds__(64 * NW)
 k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scalars* scal,
          float* st_q, float* st_g, float* samples, TraceDev tr, unsigned long long* xch,
@@ -477,20 +232,28 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
     static_assert(NSH <= kLrMaxShared, "shared parameters");
     constexpr bool CF = FORM >= 0;      // the form is fixed at compile time
     static_assert(!CF || lf_nroles(FORM) == NSH, "record slots of a compile-time form");
-    constexpr int NB = 2 * NW;          // chains per block: wave w owns chains 2w, 2w + 1
+    constexpr bool DENSE = DN > 0;
+    static_assert(!DENSE || (DN == NW && DN >= 2 && DN <= kLrSlices && !X1 && !XL),
+                  "dense: wave w is slice w, records through LDS");
+    // chains per block: wave w owns chains 2w, 2w + 1 (dense: the block's one pair)
+    constexpr int NB = DENSE ? 2 : 2 * NW;
     constexpr int NV = 2 * (NSH + 1);   // per-step pairs: lp and the shared cotangents
     constexpr int NPAIR = NV + 4;       // + K0 (first step) and K1 (last step)
     constexpr int NPASS = (NPAIR + 3) / 4, NPASS_V = (NV + 3) / 4;
     constexpr int NRS = (NV + 7) / 8;   // reduce-scatter calls per step
-    if (!X1 && A.fault && blockIdx.x == gridDim.x - 1) return;  // test hook: never publishes
+    if (!X1 && !DENSE && A.fault && blockIdx.x == gridDim.x - 1)
+        return;  // test hook: never publishes
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const mc_run_config& cfg = A.cfg;
     const int tid = threadIdx.x;
     const int wave = tid >> 6, j = tid & 63;
-    const int S = P.S, D = P.D, Dsh = P.Dsh;
+    const int S = DENSE ? DN : P.S, D = P.D, Dsh = P.Dsh;
     int64_t grp;
     int slice;
-    {
+    if constexpr (DENSE) {
+        grp = blockIdx.x;
+        slice = wave;
+    } else {
         const int64_t w = blockIdx.x, nwg = gridDim.x;
         if (nwg % 8 == 0 && (nwg / 8) % S == 0) {  // a block's slices share an XCD (speed only)
             const int64_t x = w & 7, r = w >> 3;
@@ -503,7 +266,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
     }
     const int64_t C = cfg.num_chains;
     const int64_t cbase = chain_base + grp * NB;
-    const int b0 = 2 * wave;
+    const int b0 = DENSE ? 0 : 2 * wave;
     int64_t cc[2];
     bool live[2];
 #pragma unroll
@@ -512,15 +275,15 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
         cc[c] = min(cbase + b0 + c, C - 1);
     }
 
-    float* sd = smem;
+    // LDS: (dense: the record lines [parity][slice][16], then) the scalar
+    // terms.  The slice block stays in global memory: a step reads no
+    // observation (lf_moments), and the run lengths come with the constants.
+    float* const xl = smem;
     const int64_t* blk = P.blocks + 4 * (int64_t)slice;
-    const int64_t doff = blk[0];
-    const int dlen = (int)blk[1];
+    const float* gd = P.data + blk[0];
     const int nsweep = (int)(blk[3] & 255);
     const int ndirect = (int)((blk[3] >> 8) & 255);
-    for (int i = tid; 4 * i < dlen; i += 64 * NW)
-        *(float4*)(sd + 4 * i) = *(const float4*)(P.data + doff + 4 * i);
-    LrSterm* sst = (LrSterm*)(smem + P.sdata_floats);
+    LrSterm* sst = (LrSterm*)(smem + (DENSE ? 2 * DN * 16 : 0));
     for (int i = tid; i < P.n_sterms * (int)(sizeof(LrSterm) / 16); i += 64 * NW)
         ((float4*)sst)[i] = ((const float4*)P.sterms)[i];
 
@@ -627,7 +390,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
         wtot[c] = scal[cc[c]].warmup_total;
     }
     MC_STAMP_INIT
-    __syncthreads();  // the slice block is in LDS
+    __syncthreads();  // the scalar terms are in LDS
 
     // the lane's own prior (lr_own_prior keys it by ordinal); it enters
     // slice 0's log-p record through this lane
@@ -646,39 +409,25 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
         const bool out = own.hn && !(v >= 0.0f);
         return (out || !own.on) ? 0.0f : o_wn * -(d * o_cinv2);
     };
-    // per slot: the swept term's run (data pointer, length, full float4
-    // groups of every lane) and the direct term's presence
-    const float* xv[RS];
-    int len[RS], lmin4[RS], lmax[RS];
+    // per slot: the swept term's run — its constants and element count
+    // (LrCtx::mom) — and the direct term's presence
+    int len[RS];
     f2 cnt[RS];
-    float mc_c[RS], mc_R[RS];  // the run's centre and centred sum (lf_run_consts), pinned
+    LfMom mom[RS];
     bool pdir[RS];
 #pragma unroll
     for (int r = 0; r < RS; ++r) {
-        len[r] = 0;
-        lmin4[r] = 0;
-        lmax[r] = 0;
-        xv[r] = sd;
-        if (SW && r < tt[0].nslot) {
-            len[r] = ((const int32_t*)sd)[tt[0].len_off + r * 64 + j];
-            lmin4[r] = tt[0].lmin4[r];
-            xv[r] = sd + tt[0].doff[0] + tt[0].toff[r] + 4 * j;
-        }
-        cnt[r] = bc2((float)len[r]);
-        {
-            const f2 cr = lf_run_consts(xv[r], len[r]);
-            mc_c[r] = vpin(cr[0]);
-            mc_R[r] = vpin(cr[1]);
-        }
-        // the slot's longest run (uniform: a wave max, once per launch)
-        {
-            int m = len[r];
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) m = max(m, __shfl_xor(m, o));
-            lmax[r] = __builtin_amdgcn_readfirstlane(m);
-        }
+        float4 m = {0.f, 0.f, 0.f, 0.f};
+        if (SW && r < tt[0].nslot) m = P.mom[((int64_t)slice * kLrMaxSlots + r) * 64 + j];
+        len[r] = (int)m.w;
+        cnt[r] = bc2(m.w);
+        mom[r].c = vpin(bc2(m.x));
+        mom[r].R = vpin(bc2(m.y));
+        mom[r].R2 = vpin(bc2(m.y + m.y));
+        mom[r].Q = vpin(bc2(m.z));
+        mom[r].n = cnt[r];
         pdir[r] = DIR && r < tt[nsweep].nslot &&
-                  ((const int32_t*)sd)[tt[nsweep].len_off + r * 64 + j] > 0;
+                  ((const int32_t*)gd)[tt[nsweep].len_off + r * 64 + j] > 0;
     }
     // the terms' constants, pinned in VGPRs
     const f2 sw_w = vpin(bc2(F.sw_w)), sw_c0 = vpin(bc2(F.sw_c0));
@@ -692,37 +441,6 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
              d_clogs = vpin(bc2(F.d_clogs));
     const f2 half = bc2(0.5f), one = bc2(1.0f);
     const float lp_const = vpin(P.lp_const);
-    // the swept terms' second-moment sums at the current point, both chains (a
-    // lane without elements never writes its sums: they stay the zeros they
-    // are declared with, so no zeros are materialised per sweep); the first
-    // moment is formed from the position and the run's constants where the
-    // step finishes the term (lf_m1)
-    // PRE — one slot, a compile-time form and one lane per parameter compiled
-    // in (LFS_REP1: whole runs, several rounds a sweep; the Large shape): the
-    // step issues the sweep's first loads itself (sweep_issue, ahead of the
-    // work between two sweeps: 32 registers in flight over it, 206 -> 245
-    // VGPRs) and the rounds' order is pinned (lf_moments_pre).  Every other
-    // instantiation keeps lf_moments: split runs are a round or none long,
-    // and there the early loads and their scheduling barrier in the step cost
-    // more than they hid (same-box A/B: medium -1.4 %, small -4.1 %); the
-    // run-time form went past 256 registers with them, and with more slots
-    // the register sets went to scratch.
-    constexpr bool PRE = RS == 1 && CF && (SPEC & LFS_REP1) != 0;
-    auto sweep_issue = [&](LfPre& pre) {
-        if constexpr (PRE) lf_issue<true>(xv[0], lmin4[0], pre);
-    };
-    auto sweep = [&](f2 (&s2)[RS], LfPre& pre) {
-#pragma unroll
-        for (int r = 0; r < RS; ++r) {
-            if (len[r] > 0) {
-                if constexpr (PRE)
-                    lf_moments_pre<true>(xv[r], len[r], lmin4[r], lmax[r], q[r], pre, s2[r]);
-                else
-                    lf_moments<RS == 1>(xv[r], len[r], lmin4[r], lmax[r], q[r], s2[r]);
-            }
-        }
-    };
-
     const int L = cfg.num_leapfrog_steps;
     uint32_t epoch = ebase;  // tags continue across launches (host.h ws_reserve)
     bool ok = true;
@@ -732,13 +450,18 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
     unsigned long long* gline[2];
 #pragma unroll
     for (int par = 0; par < 2; ++par)
-        gline[par] = xch + (((int64_t)par * n_groups + grp) * (NB / 2) + wave) * S * 16;
+        gline[par] = DENSE ? nullptr
+                           : xch + (((int64_t)par * n_groups + grp) * (NB / 2) + wave) * S * 16;
     const int row = j >> 4, col = j & 15;
     const bool poll_lane = col < S;
     // the poll address of pass 0 (pass ps: + 4 ps), per epoch parity
     unsigned long long* gp[2];
 #pragma unroll
-    for (int par = 0; par < 2; ++par) gp[par] = gline[par] + min(col, S - 1) * 16 + lf_row(row);
+    for (int par = 0; par < 2; ++par)
+        gp[par] = DENSE ? nullptr : gline[par] + min(col, S - 1) * 16 + lf_row(row);
+    // dense: the same lines in LDS, a float per pair (no tags), [parity][slice][16]
+    const int lpoll = min(col, S - 1) * 16 + lf_row(row);
+    auto lput = [&](int par, int off, float v) { xl[par * (DN * 16) + off] = v; };
     // publishing: lanes 16 r + n (n < NRS * 2) hold pair 8 (n / 2) + 4 (n % 2) + perm[r]
     const int pub_pair = (col < 2 * NRS) ? 8 * (col >> 1) + 4 * (col & 1) + lf_row(row) : -1;
     const bool pub_rec = pub_pair >= 0 && pub_pair < NV;
@@ -763,7 +486,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
     // of each slice's parity-0 line of wave 0 (record pairs use 0 .. NPAIR - 1
     // < 15); its tag ebase + 1 is never 0, the value of a freshly cleared
     // line (the steps' tags start there too, on the record granules).  Its
-    // loads are issued here and completed after the first sweep.
+    // loads are issued here and completed after the first drift.
     constexpr bool xchk = XL && !X1;
     unsigned long long* const xslots = xch + ((int64_t)grp * (NB / 2)) * S * 16 + 15;
     XcdPoll xpoll = {0ull};
@@ -778,9 +501,9 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
     // per-lane path uses); the normals are fetched from their lanes.  They
     // depend on the counters alone, so an iteration's are drawn while the
     // last step of the iteration before waits for its exchange (nothing else
-    // covers that wait: no sweep follows the last step), the launch's first
+    // covers that wait: no drift follows the last step), the launch's first
     // ahead of the loop — in the kernels of the Large shape's layout
-    // (DRAW_AHEAD: those with the sweep's prefetch, see PRE above); every
+    // (DRAW_AHEAD: one slot, a compile-time form, one lane per parameter); every
     // other instantiation draws at the iteration's start, as before.
     constexpr bool DRAW_AHEAD = RS == 1 && CF && (SPEC & LFS_REP1) != 0;
     f2 nx_z[RS];
@@ -960,14 +683,8 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             sh.iv = sh.is * sh.is;
             gown = vpin(own_grad(sh.v));  // for the step at this position
         };
-        f2 M2[RS];
-#pragma unroll
-        for (int r = 0; r < RS; ++r) M2[r] = (f2){0.f, 0.f};
-        LfPre pre;
-        sweep_issue(pre);
         drift_private(false);
         drift_shared(false);
-        sweep(M2, pre);
         if (xchk && it == cfg.iter_begin) {  // (before the launch's first publish)
             const bool same = xcd_agree(xpoll, xslots, S, ebase + 1, ok);
             // (diagnostic: blocks found on one XCD / not, counted by slice 0,
@@ -1001,7 +718,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             // no vector-memory operation is in flight here (the last poll was
             // waited for): saying so explicitly keeps the compiler's wait-count
             // state clean at the step's entry, where the kinds' paths merge —
-            // else it guards the sweep's first register writes with a
+            // else it guards the step's first register writes with a
             // vmcnt(0) that also waits for this step's own publish store
             __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
             if constexpr (LAST)  // the shared scales' logs, for log p (log2 v * ln 2)
@@ -1028,6 +745,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             };
             // (a shared scale's 1/s^2 is squared here from its 1/s: the
             // holding lane's sh.iv = sh.is * sh.is, the same rounding)
+            f2 M2[RS];
             if (SW) {
                 const f2 is = SWS ? lf_sh2(sh.is, ksw) : sw_cinv;
                 const f2 iv = SWS ? is * is : sw_cinv2;
@@ -1035,15 +753,16 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                 for (int r = 0; r < RS; ++r) {
                     const bool on = len[r] != 0;
                     const f2 z = {0.f, 0.f};
-                    // the first moment at q[r], where the sweep ran (the
-                    // drift to the next position follows this finish): the
-                    // data's share is the run's constants; an empty lane's
-                    // stays the zero the skipped sweep left
-                    const f2 m1 = lf_m1(cnt[r], mc_c[r], mc_R[r], q[r]);
+                    // both moment sums at q[r] from the run's constants (the
+                    // drift to the next position follows this finish); an
+                    // empty lane's are zeros whatever its position is
+                    f2 m1, m2;
+                    lf_moments(mom[r], q[r], m1, m2);
                     const f2 M1r = on ? m1 : z;
+                    M2[r] = on ? m2 : z;
                     if (RS == 1) {
                         // one slot: an empty lane's moment sums and count are
-                        // zeros (the sweep skips it), so are its gradient and
+                        // zeros, so are its gradient and
                         // cotangent; its log p is selected away
                         g[r] = sw_w * (M1r * iv);
                         cs = sw_w * ((M2[r] * iv - cnt[r]) * is);
@@ -1119,9 +838,6 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                 }
             }
             MC_STAMP(1);
-            // the next sweep's first loads (they do not depend on the position):
-            // in flight over the reduce-scatter, the publish and the drift
-            if constexpr (!LAST) sweep_issue(pre);
             // wave totals, reduce-scattered: pair P = 2 slot + chain
             float xr[2 * NRS];
             {
@@ -1183,7 +899,11 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                 float pv = xr[0];
 #pragma unroll
                 for (int x = 1; x < 2 * NRS; ++x) pv = (x == pub_x) ? xr[x] : pv;
-                if (pub_mid) granule_put(gline[par] + pub_off, epoch, pv, XL);
+                if constexpr (DENSE) {
+                    if (pub_mid) lput(par, pub_off, pv);
+                } else {
+                    if (pub_mid) granule_put(gline[par] + pub_off, epoch, pv, XL);
+                }
             } else if (!X1) {
                 // one store instruction: the record pairs, and the K items on the
                 // first / last step (lanes 2, 3 of rows 0 / 1)
@@ -1207,16 +927,16 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                         pv = c ? k1w[1] : k1w[0];
                     }
                 }
-                if (pp >= 0) granule_put(gline[par] + slice * 16 + pp, epoch, pv, XL);
+                if constexpr (DENSE) {
+                    if (pp >= 0) lput(par, slice * 16 + pp, pv);
+                } else {
+                    if (pp >= 0) granule_put(gline[par] + slice * 16 + pp, epoch, pv, XL);
+                }
             }
             MC_STAMP(2);
-            // the sweep issues at a higher wave priority than the latency-bound
-            // rest of the step (slice sums, shared drift, finish, reduce-scatter,
-            // publish): the two waves of a SIMD settle out of phase, one
-            // sweeping while the other's dependent chains fill its gaps (with
-            // equal priorities the SQ's oldest-first choice kept them in step;
-            // A/B on one box 92.0 -> 100.0 M steps/s, the same with priority 1, 2
-            // or 3, and with the poll at either level, profiles/r3/ab/ab34)
+            // (a higher wave priority from here to the end of the poll: tuned
+            // while a sweep ran here, profiles/r3/ab/ab34, and not measured
+            // again since it left; every figure of DESIGN.md section 4 is with it)
             __builtin_amdgcn_s_setprio(1);
             // poll: pass ps reads pair 4 ps + perm[row] of slice col
             constexpr bool kstep = FIRST || LAST;
@@ -1238,17 +958,13 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                     y[ps] = (ps < NPASS_V || kstep) ? granule_load(gp[par] + 4 * ps) : 0ull;
             };
             // while the records travel: the private parameters' next position
-            // and the swept terms' sums there (a poll issued inside the sweep
-            // costs a second round trip when the records have not landed yet:
-            // A/B 83.2 vs 94.7 M steps/s, profiles/r4/ab)
-            if constexpr (!LAST) {
-                drift_private(true);
-                sweep(M2, pre);
-            }
+            // (a poll issued before the records have landed costs a second
+            // round trip: A/B 83.2 vs 94.7 M steps/s, profiles/r4/ab)
+            if constexpr (!LAST) drift_private(true);
             // the last step: the next iteration's draws, while the records travel
             if constexpr (LAST) ahead();
             MC_STAMP(8);
-            if (!X1) poll_issue();
+            if (!X1 && !DENSE) poll_issue();
             auto poll_eval = [&]() {
                 bool ready = true;  // (bitwise: lane masks, no branches)
 #pragma unroll
@@ -1261,7 +977,20 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                 }
                 return ready;
             };
-            bool ready = X1 ? true : poll_eval();
+            if constexpr (DENSE) {
+                // the block's records are in the line after one barrier; a
+                // wave writes this parity's line again two steps on, past the
+                // next step's barrier, which every wave reaches only after
+                // these reads
+                __syncthreads();
+#pragma unroll
+                for (int ps = 0; ps < NPASS; ++ps) {
+                    const bool nd = ((need >> ps) & 1u) != 0u;
+                    const float v = (ps < NPASS_V || kstep) ? xl[par * (DN * 16) + lpoll + 4 * ps] : 0.0f;
+                    vals[ps] = nd ? v : 0.0f;
+                }
+            }
+            bool ready = (X1 || DENSE) ? true : poll_eval();
             MC_STAMP(7);
             uint32_t spins = 0;
             while (__ballot(!ready)) {

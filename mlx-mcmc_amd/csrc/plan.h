@@ -112,6 +112,7 @@ inline hipError_t upload_lanes(LanePlan& LP) {
     if (e == hipSuccess) e = upload(&LP.d_gidx, LP.gidx);
     if (e == hipSuccess && !LP.sterms.empty()) e = upload(&LP.d_sterms, LP.sterms);
     if (e == hipSuccess && !LP.rng.empty()) e = upload(&LP.d_rng, LP.rng);
+    if (e == hipSuccess && !LP.mom.empty()) e = upload(&LP.d_mom, LP.mom);
     return e;
 }
 inline int upload_failed(hipError_t e, const char* what) {

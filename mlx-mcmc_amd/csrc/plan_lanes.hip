@@ -12,6 +12,7 @@ void free_lanes(LanePlan& L) {
     if (L.d_gidx) (void)hipFree(L.d_gidx);
     if (L.d_sterms) (void)hipFree(L.d_sterms);
     if (L.d_rng) (void)hipFree(L.d_rng);
+    if (L.d_mom) (void)hipFree(L.d_mom);
     L = LanePlan();
 }
 
@@ -214,6 +215,7 @@ static int lane_geometry(const mc_program* p, const SlPartition& part, LanePlan&
             const int cap = std::atoi(e);
             while (rep > 1 && rep > cap) rep >>= 1;
         }
+        while (L.rep_cap > 0 && rep > L.rep_cap) rep >>= 1;
     }
     for (int t = 0; t < nT; ++t) {
         if (part.scalar[t] || part.ppr[t] < 0) continue;
@@ -426,6 +428,38 @@ static int tile_lane_term(const mc_program* p, int t, const LaneLists& lists, in
     return MC_OK;
 }
 
+// The moment constants of slice s's first swept term `lt` (block at blk0), per
+// (slot, lane) run exactly as the tile holds it (with rep > 1: a lane's own
+// part of the run): n its element count, c = (float) mean(x),
+// R = (float) sum (x - c), Q = (float) sum (x - c)^2 — float64 sums in element
+// order, rounded once (c and R contain no multiply: the bits do not depend on
+// the host compiler's contraction).  An empty run: zeros.  lanes_fast.h
+// lf_moments forms both moment sums at any position from them.
+static void lane_moments(LanePlan& L, int s, int64_t blk0, const LrTerm& lt) {
+    const float* base = &L.data[blk0 + lt.doff[0]];
+    const int32_t* lens = (const int32_t*)&L.data[blk0 + lt.len_off];
+    for (int r = 0; r < lt.nslot && r < kLrMaxSlots; ++r)
+        for (int l = 0; l < 64; ++l) {
+            const int64_t n = lens[r * 64 + l];
+            if (n <= 0) continue;
+            const float* x = base + lt.toff[r] + 4 * l;
+            auto at = [&](int64_t u) { return (double)x[(u >> 2) * 256 + (u & 3)]; };
+            double sum = 0.0, sr = 0.0, sq = 0.0;
+            for (int64_t u = 0; u < n; ++u) sum += at(u);
+            const float c = (float)(sum / (double)n);
+            for (int64_t u = 0; u < n; ++u) sr += at(u) - (double)c;
+            for (int64_t u = 0; u < n; ++u) {
+                const double d = at(u) - (double)c;
+                sq += d * d;
+            }
+            float* m = &L.mom[(((size_t)s * kLrMaxSlots + r) * 64 + l) * 4];
+            m[0] = c;
+            m[1] = (float)sr;
+            m[2] = (float)sq;
+            m[3] = (float)n;
+        }
+}
+
 // The scalar terms, compact (LDS copy in every workgroup).  Returns the number
 // of them k_hmc_lf cannot take.
 static int lane_sterms(const SlPartition& part, LanePlan& L) {
@@ -477,6 +511,7 @@ int plan_lanes(const mc_program* p, const SlPartition& part, LanePlan& L) {
     L.blocks.assign(4 * (size_t)S, 0);
     L.gidx.assign((size_t)S * kLrMaxSlots * 64, -1);
     L.sdata_floats = 0;
+    L.mom.assign((size_t)S * kLrMaxSlots * 64 * 4, 0.0f);
     std::vector<int> lane_of(p->D, -1), slot_of_p(p->D, -1);
     bool any_rest = false, any_rest_nonexpr = false;
     for (int s = 0; s < S; ++s) {
@@ -516,6 +551,7 @@ int plan_lanes(const mc_program* p, const SlPartition& part, LanePlan& L) {
                             (!swept.empty() && swept[0].sig != LS_DATA_PP_SH &&
                              swept[0].sig != LS_DATA_PP_C));
         if (!rest.empty() || !core) any_rest = true;
+        if (core && !swept.empty()) lane_moments(L, s, blk0, swept[0]);
         bool rest_expr = true;  // every other term an expression term (LanePlan::nuts_expr)
         for (const LrTerm& lt : rest) rest_expr &= lt.sig == LS_EXPR;
         if (!rest_expr || !core) any_rest_nonexpr = true;

@@ -236,9 +236,81 @@ static int plan_lanes1(mc_program* p) {
     return MC_OK;
 }
 
+// The dense HMC plan (mc_program::lrd), beside an automatic program-level plan
+// that is fast-form with the hierarchical compile-time form and no transformed
+// shared parameter: the same planner passes at one lane per parameter on DS
+// slices.  A step of k_hmc_lf reads no observation (lanes_fast.h lf_moments),
+// so nothing is gained by spreading a chain pair's sweep over workgroups: a
+// pair runs in one.  DS = 1 — one wave, no exchange — when the private
+// parameters fit a wave's 64 lanes x 4 slots; else the fewer of 4 and 8 waves
+// that hold them at two slots per lane, exchanging through LDS (measured on
+// D = 1000: 8 waves x 2 slots 244 M leapfrog-steps/s, 4 x 4 219 M, the 16
+// exchanging workgroups 239 M).  More than 1024 private
+// parameters keep the exchange kernels: 16 waves of one workgroup would need
+// the kernel in 128 VGPRs.  MC_HMC_DENSE=0 in the environment turns the
+// route off (A/B against the exchange kernels).  The plan's data tables are
+// uploaded with it though the kernel reads only the direct term's length
+// table of them: known slack.
+static void plan_hmc_dense(mc_program* p) {
+    constexpr int HIER = LF_SW | LF_SWS | LF_DIR | LF_DM | LF_DS;
+    if (!env_on("MC_HMC_DENSE")) return;
+    if (!p->lr.ok || !p->lr.fast || p->lr.form != HIER || p->lr.has_xf || p->lr.has_expr) return;
+    const int priv = p->D - p->lr.Dsh;
+    int DS = 1;
+    if (priv > 64 * kLrMaxSlots) {
+        DS = (priv + 3) / 4 <= 128 ? 4 : 8;
+        if ((priv + DS - 1) / DS > 128) return;
+    }
+    SlicePlan P;
+    SlPartition part;
+    LanePlan& L = p->lrd;
+    L.rep_cap = 1;
+    const bool ok = plan_slices(p, DS, P, part) == MC_OK && plan_lanes(p, part, L) == MC_OK &&
+                    L.fast && L.form == HIER && L.rep == 1 && L.S == DS && !L.has_xf &&
+                    (DS == 1 || L.rs == 2) && upload_lanes(L) == hipSuccess;
+    if (!ok) free_lanes(L);
+}
+
+static int set_slices(mc_program* p, int32_t S);
 extern "C" int mc_program_set_slices(mc_program* p, int32_t S) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
     if (S < 0 || S > 64) return fail(MC_ERR_INVALID, "num_slices must be in [0, 64]");
+    free_lanes(p->lrd);
+    const int rc = set_slices(p, S);
+    // an explicit slice count always runs the program-level kernels
+    if (rc == MC_OK && S == 0) {
+        const std::string err = g_last_error;  // (a declined dense plan is no error)
+        plan_hmc_dense(p);
+        g_last_error = err;
+    }
+    return rc;
+}
+
+// 1 when HMC launches of the program take the dense route (run_hmc.hip), with
+// its slices (waves per chain pair) and register slots per lane; else 0
+extern "C" int32_t mc_program_hmc_dense(const mc_program* p, int32_t* slices, int32_t* slots) {
+    if (!p) return -1;
+    const bool on = hmc_dense_route(p);
+    if (slices) *slices = on ? p->lrd.S : 0;
+    if (slots) *slots = on ? p->lrd.rs : 0;
+    return on ? 1 : 0;
+}
+
+// Test hook: the moment constants (c, R, Q, n) of the program-level lane plan
+// (host table; LanePlan::mom), [S][kLrMaxSlots][64][4] floats.  Returns the
+// number of floats, or a negative error code.
+extern "C" int64_t mc_debug_lane_moments(const mc_program* p, float* out, int64_t n_out) {
+    if (!p) return -(int64_t)fail(MC_ERR_INVALID, "program is NULL");
+    if (!p->lr.ok) return -(int64_t)fail(MC_ERR_UNSUPPORTED, "the program has no lane plan");
+    const int64_t n = (int64_t)p->lr.mom.size();
+    if (out) {
+        if (n_out < n) return -(int64_t)fail(MC_ERR_INVALID, "out holds %lld floats", (long long)n);
+        std::copy(p->lr.mom.begin(), p->lr.mom.end(), out);
+    }
+    return n;
+}
+
+static int set_slices(mc_program* p, int32_t S) {
     const bool automatic = (S == 0);
     if (automatic) S = auto_slices(p);
     free_slices(p->sl);
@@ -1190,6 +1262,7 @@ extern "C" int mc_program_destroy(mc_program* p) {
     pw_free(p);
     free_slices(p->sl);
     free_lanes(p->lr);
+    free_lanes(p->lrd);
     if (p->d_terms) (void)hipFree(p->d_terms);
     if (p->d_nodes) (void)hipFree(p->d_nodes);
     if (p->d_data) (void)hipFree(p->d_data);

@@ -222,6 +222,13 @@ extern "C" int mc_hmc_run(const mc_program* p, const mc_run_config* cfg, void* s
             return fail(MC_ERR_INVALID, "workspace too small: need %lld bytes", (long long)need);
         if (device_cus() <= 0) return fail(MC_ERR_HIP, "no HIP device");
         hipStream_t st = (hipStream_t)stream;
+        if (use_lanes(p, cfg) && hmc_dense_route(p)) {
+            switch (p->lrd.rs) {
+                case 1: return hmc_dense_rs1(p, cfg, state, samples, tr, ws, st);
+                case 2: return hmc_dense_rs2(p, cfg, state, samples, tr, ws, st);
+                default: return hmc_dense_rs4(p, cfg, state, samples, tr, ws, st);
+            }
+        }
         if (!use_lanes(p, cfg))
             return sl_nb_for(p, cfg->num_chains) == 16
                        ? launch_hmc_sl<16>(p, cfg, state, samples, tr, ws, st)

@@ -8,7 +8,7 @@
 template <int NW, bool X1, typename K>
 inline int hmc_lr_exchange(const char* name, K& k, const mc_program* p, const mc_run_config* cfg,
                            void* state, float* samples, const mc_trace* tr, void* ws,
-                           hipStream_t st) {
+                           hipStream_t st, bool fast = false) {
     RunState R = run_state(p, cfg, state);
     const LrCtx ctx = lrctx_of(p);
     const TraceDev td = trace_of(tr);
@@ -18,7 +18,8 @@ inline int hmc_lr_exchange(const char* name, K& k, const mc_program* p, const mc
     d.threads = 64 * NW;
     d.chains = NB;
     d.S = p->lr.S;
-    d.lds = lr_base_lds_bytes(p);
+    // (k_hmc_lf keeps only the scalar terms in LDS: its steps read no observation)
+    d.lds = fast ? p->lr.sterms.size() * sizeof(LrSterm) : lr_base_lds_bytes(p);
     d.blocks_per_launch = lr_groups_per_launch(p, cfg->num_chains);  // (X1: all of them)
     d.clear_bytes = sl_workspace_bytes(p, cfg->num_chains);
     d.tags_per_launch = (uint64_t)cfg->iter_count * cfg->num_leapfrog_steps + 1;
@@ -75,7 +76,42 @@ inline int launch_hmc_lr(const mc_program* p, const mc_run_config* cfg, void* st
         }
     }
     auto k = static_pair(kern, kern_xl);
-    return hmc_lr_exchange<NW, X1>("lane-resident HMC", k, p, cfg, state, samples, tr, ws, st);
+    return hmc_lr_exchange<NW, X1>("lane-resident HMC", k, p, cfg, state, samples, tr, ws, st,
+                                   fast);
+}
+
+// The dense launch (mc_program::lrd; lanes_fast.h DN): one workgroup per chain
+// pair, no exchange workspace, tags, co-residency check or status word — the
+// grid is the chain pairs, however many the device holds at once.  One slice:
+// the X1 kernel (a wave per workgroup); DS slices: DS waves exchanging through
+// LDS, which by the plan's choice of DS have 2 register slots.
+template <int RS>
+inline int launch_hmc_dense(const mc_program* p, const mc_run_config* cfg, void* state,
+                            float* samples, const mc_trace* tr, void* ws, hipStream_t st) {
+    constexpr int HIER = LF_SW | LF_SWS | LF_DIR | LF_DM | LF_DS;
+    constexpr int PLAIN = LFS_REP1 | LFS_NOXF;
+    constexpr int NSH = lf_nroles(HIER);
+    const LanePlan& L = p->lrd;
+    RunState R = run_state(p, cfg, state);
+    const LrCtx ctx = lrctx_of(p, L);
+    const TraceDev td = trace_of(tr);
+    ws_forget(ws);  // (no status word: mc_workspace_status has nothing to read)
+    const int64_t groups = (cfg->num_chains + 1) / 2;
+    const size_t sterm_bytes = L.sterms.size() * sizeof(LrSterm);
+    auto go = [&](auto kern, int waves) {
+        const size_t lds = sterm_bytes + (waves > 1 ? (size_t)2 * waves * 16 * 4 : 0);
+        hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(64 * waves), lds, st, ctx, R.A,
+                           (int64_t)0, groups, R.scalars, R.q, R.g, samples, td,
+                           (unsigned long long*)nullptr, (int*)nullptr, (uint32_t)0);
+        MC_HIP_TRY(hipGetLastError());
+        return MC_OK;
+    };
+    if (L.S == 1) return go(k_hmc_lf<RS, NSH, 1, true, HIER, false, PLAIN>, 1);
+    if constexpr (RS == 2) {
+        if (L.S == 4) return go(k_hmc_lf<2, NSH, 4, false, HIER, false, PLAIN, 4>, 4);
+        if (L.S == 8) return go(k_hmc_lf<2, NSH, 8, false, HIER, false, PLAIN, 8>, 8);
+    }
+    return fail(MC_ERR_UNSUPPORTED, "dense HMC: no kernel for %d slices at %d slots", L.S, RS);
 }
 
 // NSH (3 or 4 shared parameters) x waves per workgroup (one slice: 1 wave and

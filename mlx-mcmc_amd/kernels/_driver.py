@@ -256,6 +256,9 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
                             else program.slice_kernel)
     if note and algorithm == "hmc":
         info.extra["kernel_note"] = note
+    if algorithm == "hmc" and not use_metric and program.hmc_dense:
+        # (slices, slots) of the dense route: a chain pair per workgroup
+        info.extra["hmc_dense"] = program.hmc_dense
     if use_metric and not metric_lanes:
         info.extra["kernel_note"] = ("a mass matrix runs on the chain-per-workgroup tape kernel "
                                      f"(k_{algorithm}), as num_slices=1 does")
