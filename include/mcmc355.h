@@ -330,6 +330,13 @@ int32_t mc_program_lane_bundle(const mc_program* prog);
  * NUTS, MH and the pointwise kernels always run the program-level plan.
  * -1 on a null program.                                                     */
 int32_t mc_program_hmc_dense(const mc_program* prog, int32_t* slices, int32_t* slots);
+/* Test hook: how the dense HMC route draws its momenta and accept uniforms.
+ * 0: HMC launches run the program-level plan; 1: the dense plan has a lane RNG
+ * plan (a Philox block per lane); 2: it has none and the workgroup draws every
+ * block once, handing the normals out through LDS; 3: none, and every lane
+ * draws its own (MC_HMC_DENSE_RNG=0 when the plan was made).  The draws are the
+ * same bits in every mode.  -1 on a null program.                              */
+int32_t mc_debug_hmc_dense_rng(const mc_program* prog);
 /* Why the program's HMC launches do not run the lane-resident kernel (e.g.
  * "lane-resident kernel: more than 4 broadcast parameters"), or "" when they
  * do or no plan was attempted; valid until the next set_slices /

@@ -1472,6 +1472,16 @@ class Program:
         return (int(s.value), int(r.value)) if on == 1 else None
 
     @property
+    def hmc_dense_rng(self):
+        """How the dense HMC route draws (mc_debug_hmc_dense_rng): "plan" — the
+        lane RNG plan, a Philox block per lane; "block" — no such plan, every
+        block drawn once per workgroup and handed out through LDS; "lane" — no
+        plan and MC_HMC_DENSE_RNG=0: every lane draws its own; None when HMC
+        launches run the program-level plan."""
+        k = int(_lib.load().mc_debug_hmc_dense_rng(self.handle))
+        return {1: "plan", 2: "block", 3: "lane"}.get(k)
+
+    @property
     def lane_bundle(self) -> int:
         """Widest bundle of private parameters one element of a gathered
         expression term reads on the lane-resident plan (alpha[g] + beta[g] * x:

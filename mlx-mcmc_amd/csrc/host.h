@@ -122,6 +122,8 @@ struct LanePlan {
     std::vector<float> mom;
     float* d_mom = nullptr;
     int rep_cap = 0;     // > 0: the planner keeps rep <= rep_cap (the dense HMC plan: 1)
+    int blk_rng = 0;     // the dense HMC plan, no lane RNG plan: block-wide draws
+                         // (lanes.h LrCtx::blk_rng; program.hip plan_hmc_dense)
     int has_xf = 0;      // a shared parameter is transformed, or an identity term
                          // (no NUTS lanes, no term interpreter)
     int has_expr = 0;    // LS_EXPR terms: only the JIT-compiled k_hmc_lr runs the plan
@@ -412,6 +414,7 @@ inline LrCtx lrctx_of(const mc_program* p, const LanePlan& L) {
     }
     c.has_xf = L.has_xf;
     c.rep = L.rep;
+    c.blk_rng = L.blk_rng;
     c.rng = (const int4*)L.d_rng;
     c.mom = (const float4*)L.d_mom;
     return c;

@@ -149,6 +149,11 @@ struct LrCtx {
                                  // .. + rep-1), every lane of the group holds
                                  // its q, p, g; the group leader alone counts it
                                  // in kinetic energies, U-turn dots and stores
+    int32_t blk_rng;             // the dense HMC plan without a lane RNG plan:
+                                 // the workgroup draws every Philox block once
+                                 // and hands the normals out through LDS
+                                 // (lanes_fast.h draw_block); 0: every lane
+                                 // draws its own
 };
 
 typedef float f2 __attribute__((ext_vector_type(2)));

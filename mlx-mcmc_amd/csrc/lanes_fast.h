@@ -168,6 +168,51 @@ MC_DEV void lf_moments(const LfMom& m, f2 th, f2& M1, f2& M2) {
     M2 = pk_fma(pk_fma(m.n, d, m.R2), d, m.Q);
 }
 
+// The job map of the block-wide draws (k_hmc_lf draw_block): with NBk =
+// ceil(D / 4) momentum blocks per chain, job t < 2 NBk is momentum block
+// t % NBk of chain t / NBk, jobs 2 NBk and 2 NBk + 1 are the accept draws of
+// chains 0 and 1; a thread of `lanes` takes jobs tid, tid + lanes, ...
+struct LfDrawJob {
+    bool acc;  // an accept draw (else a momentum block)
+    int c, b;  // chain of the pair, Philox block
+};
+constexpr int lf_draw_jobs(int D) { return 2 * ((D + 3) / 4) + 2; }
+constexpr LfDrawJob lf_draw_job(int t, int D) {
+    const int NBk = (D + 3) / 4;
+    const bool acc = t >= 2 * NBk;
+    const int c = acc ? t - 2 * NBk : (t >= NBk ? 1 : 0);
+    return {acc, c, acc ? 0 : t - (c ? NBk : 0)};
+}
+// every (chain, block) and both accept draws are taken exactly once
+constexpr bool lf_draw_jobs_once(int D, int lanes) {
+    const int NBk = (D + 3) / 4;
+    int mom[2][257] = {}, acc[2] = {};
+    if (NBk > 257) return false;
+    for (int tid = 0; tid < lanes; ++tid)
+        for (int t = tid; t < lf_draw_jobs(D); t += lanes) {
+            const LfDrawJob jb = lf_draw_job(t, D);
+            if (jb.c < 0 || jb.c > 1 || jb.b < 0 || jb.b >= NBk) return false;
+            if (jb.acc) ++acc[jb.c];
+            else ++mom[jb.c][jb.b];
+        }
+    for (int c = 0; c < 2; ++c) {
+        if (acc[c] != 1) return false;
+        for (int b = 0; b < NBk; ++b)
+            if (mom[c][b] != 1) return false;
+    }
+    return true;
+}
+static_assert(lf_draw_jobs(1000) == 502 && lf_draw_jobs(1027) == 516, "Large: one trip of 512");
+static_assert(lf_draw_jobs_once(4, 64) && lf_draw_jobs_once(4, 256) && lf_draw_jobs_once(4, 512) &&
+              lf_draw_jobs_once(5, 64) && lf_draw_jobs_once(5, 256) && lf_draw_jobs_once(5, 512) &&
+              lf_draw_jobs_once(303, 64) && lf_draw_jobs_once(303, 256) &&
+              lf_draw_jobs_once(303, 512) && lf_draw_jobs_once(1000, 64) &&
+              lf_draw_jobs_once(1000, 256) && lf_draw_jobs_once(1000, 512) &&
+              lf_draw_jobs_once(1024, 64) && lf_draw_jobs_once(1024, 256) &&
+              lf_draw_jobs_once(1024, 512) && lf_draw_jobs_once(1027, 64) &&
+              lf_draw_jobs_once(1027, 256) && lf_draw_jobs_once(1027, 512),
+              "the block-wide draws' job map");
+
 // The fast-form terms of a slice, read once per launch: at most one swept
 // term (y ~ N(theta[g], scale): value data, loc private, scale shared or
 // constant) and one direct term (theta ~ N(loc, scale), loc / scale shared or
@@ -389,8 +434,61 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
         wacc[c] = scal[cc[c]].warmup_accept;
         wtot[c] = scal[cc[c]].warmup_total;
     }
+    // Block-wide draws (LrCtx::blk_rng: a dense plan without a lane RNG plan).
+    // An iteration needs NBk = ceil(D / 4) momentum blocks per chain and one
+    // accept draw per chain, dealt to the threads by lf_draw_job (Large: 502
+    // jobs on 512 lanes, one trip).  A job is one Philox block
+    // and both Box-Muller pairs of it (mc_box_muller_log of the first
+    // uniform's log: the bits of mc_box_muller, philox.h), written as one
+    // float4 to z[c][4 b ..]; an accept job's first log is the accept log
+    // (mc_logf_unit of the accept uniform, as mc_logf_u01).  These are the
+    // counters and functions of the per-lane draws below (normal_of), so
+    // every lane reads the bits it would have drawn.  LDS, after the scalar
+    // terms, per iteration parity: z[2][4 NBk] and the two accept logs.  The
+    // draws of iteration it + 1 are made by the last step of iteration it,
+    // between its publish and its barrier, into the other parity's buffer:
+    // that buffer was last read at the start of iteration it - 1, before a
+    // barrier every wave has passed (with L = 1 too: that iteration's one
+    // step), so no barrier is added; the launch's first iteration is drawn
+    // ahead of the barrier below.
+    // Compiled into the dense launches' instantiations alone (run_lanes.h
+    // launch_hmc_dense), and of the one-wave kernels only the four-slot one,
+    // whose plans (more than 128 parameters) never have a lane RNG plan: the
+    // one-slot kernel's always have one, and the code would cost it its third
+    // wave per SIMD (167 -> 182 VGPRs); the two-slot kernel (medium) lacks one
+    // only at 117 .. 128 parameters, and keeps the per-lane draws there.
+    constexpr bool BDRAW = (DENSE || (X1 && RS == 4)) &&
+                           FORM == (LF_SW | LF_SWS | LF_DIR | LF_DM | LF_DS) &&
+                           SPEC == (LFS_REP1 | LFS_NOXF);
+    const bool bdraw = BDRAW && P.blk_rng != 0;
+    const int NBk = (D + 3) >> 2;
+    const int ZB = 8 * NBk + 4;  // floats per parity
+    static_assert(sizeof(LrSterm) % 16 == 0, "the draws' float4 stores follow the scalar terms");
+    float* const zl = (float*)sst + P.n_sterms * (int)(sizeof(LrSterm) / 4);
+    auto draw_block = [&](int64_t itd) {
+        float* const zb = zl + (int)(itd & 1) * ZB;
+        for (int t = tid; t < lf_draw_jobs(D); t += 64 * NW) {
+            const LfDrawJob jb = lf_draw_job(t, D);
+            const bool acl = jb.acc;
+            const int c = jb.c, b = jb.b;
+            const mc_u32x4 rr =
+                mc_draw(cfg.seed, (uint32_t)(cfg.chain_offset + (c ? cc[1] : cc[0])),
+                        (uint32_t)itd, acl ? MC_RNG_TAG_ACCEPT : MC_RNG_TAG_MOMENTUM, 0,
+                        acl ? 0u : (uint32_t)b);
+            const float la = mc_logf_unit(acl ? mc_u01_f32(rr.x) : mc_u01_boxf(rr.x));
+            const float lb = mc_logf_unit(mc_u01_boxf(rr.z));
+            float4 z;
+            mc_box_muller_log(la, rr.y, &z.x, &z.y);
+            mc_box_muller_log(lb, rr.w, &z.z, &z.w);
+            if (acl) zb[8 * NBk + c] = la;
+            else *(float4*)(zb + 4 * (c * NBk + b)) = z;
+        }
+    };
+    if constexpr (BDRAW) {
+        if (bdraw && cfg.iter_count > 0) draw_block(cfg.iter_begin);
+    }
     MC_STAMP_INIT
-    __syncthreads();  // the scalar terms are in LDS
+    __syncthreads();  // the scalar terms (and the first iteration's draws) are in LDS
 
     // the lane's own prior (lr_own_prior keys it by ordinal); it enters
     // slice 0's log-p record through this lane
@@ -622,6 +720,24 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                 const float zs = fetch(sh_src, xg & 3);
                 sh.p = xon ? zs : 0.0f;
             }
+        } else if (bdraw) {
+            // the block-wide draws of this iteration (draw_block), published
+            // by the barrier of the step that made them (one wave: this one)
+            if constexpr (X1) __syncthreads();
+            const float* const zb = zl + (int)(it & 1) * ZB;
+            logu_acc[0] = zb[8 * NBk];
+            logu_acc[1] = zb[8 * NBk + 1];
+#pragma unroll
+            for (int r = 0; r < RS; ++r) {
+                const int gi = max(gk[r], 0);
+                const f2 z = {zb[gi], zb[4 * NBk + gi]};
+                if (gk[r] >= 0) {  // (an empty slot's p stays 0: its g is always 0)
+                    p[r] = z;
+                    if (lead) k0p += z * z;
+                }
+            }
+            const float zs = zb[(xc ? 4 * NBk : 0) + xg];
+            sh.p = xon ? zs : 0.0f;
         } else {
 #pragma unroll
             for (int r = 0; r < RS; ++r) {
@@ -720,7 +836,11 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             // state clean at the step's entry, where the kinds' paths merge —
             // else it guards the step's first register writes with a
             // vmcnt(0) that also waits for this step's own publish store
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
+            // (not the dense step, which issues no vector-memory operation;
+            // the one-wave kernels keep it: without it and the poll's
+            // skeleton below the small shape lost 6 %, 949 -> 894 M)
+            if constexpr (!DENSE)
+                __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
             if constexpr (LAST)  // the shared scales' logs, for log p (log2 v * ln 2)
                 sh.lg = __builtin_amdgcn_logf(sh.v) * 0.693147180559945f;
             MC_STAMP(0);
@@ -936,8 +1056,10 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             MC_STAMP(2);
             // (a higher wave priority from here to the end of the poll: tuned
             // while a sweep ran here, profiles/r3/ab/ab34, and not measured
-            // again since it left; every figure of DESIGN.md section 4 is with it)
-            __builtin_amdgcn_s_setprio(1);
+            // again since it left on the exchange kernels; the dense step runs
+            // without it: Large 318.3 M without against 318.6 with, inside the
+            // run-to-run spread, profiles/lf_dense_rng)
+            if constexpr (!DENSE) __builtin_amdgcn_s_setprio(1);
             // poll: pass ps reads pair 4 ps + perm[row] of slice col
             constexpr bool kstep = FIRST || LAST;
             const uint32_t need =
@@ -990,24 +1112,30 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
                     vals[ps] = nd ? v : 0.0f;
                 }
             }
-            bool ready = (X1 || DENSE) ? true : poll_eval();
-            MC_STAMP(7);
-            uint32_t spins = 0;
-            while (__ballot(!ready)) {
-                if (++spins > kSpinLimit) {
-                    ok = false;
-                    break;
+            // (dense: nothing to wait for, no timeout — none of the poll, its
+            // spin counter or the early return is compiled)
+            if constexpr (!DENSE) {
+                bool ready = X1 ? true : poll_eval();
+                MC_STAMP(7);
+                uint32_t spins = 0;
+                while (__ballot(!ready)) {
+                    if (++spins > kSpinLimit) {
+                        ok = false;
+                        break;
+                    }
+                    // (no s_sleep between polls: the round trip paces them; A/B
+                    // medium 186.0 -> 188.8 M steps/s, large +0.3 %, profiles/r4/ab)
+                    poll_issue();
+                    ready = poll_eval();
                 }
-                // (no s_sleep between polls: the round trip paces them; A/B
-                // medium 186.0 -> 188.8 M steps/s, large +0.3 %, profiles/r4/ab)
-                poll_issue();
-                ready = poll_eval();
+                // (a timeout is reported once, after the trajectory's steps: the
+                // store's operands are not reloaded inside the step loop)
+                if (__builtin_expect(!ok, 0)) return false;
+            } else {
+                MC_STAMP(7);
             }
-            // (a timeout is reported once, after the trajectory's steps: the
-            // store's operands are not reloaded inside the step loop)
-            if (__builtin_expect(!ok, 0)) return false;
             MC_STAMP(3);
-            __builtin_amdgcn_s_setprio(0);
+            if constexpr (!DENSE) __builtin_amdgcn_s_setprio(0);
             // slice sums: a fixed 16-lane DPP tree per pass; pair 4 ps + perm[r]
             // in row r of tot[ps]
             float tot[NPASS];
@@ -1073,6 +1201,9 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             if constexpr (DRAW_AHEAD) {
                 if (rngp && it + 1 < it_end) draw_plan(it + 1);
             }
+            if constexpr (BDRAW) {
+                if (bdraw && it + 1 < it_end) draw_block(it + 1);
+            }
         };
         const std::integral_constant<int, -1> rtpar;
         if (L == 1) {
@@ -1125,7 +1256,7 @@ k_hmc_lf(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_scal
             const float H1 = -lpn[c] + 0.5f * (K1[c] + k1s[c]);
             const float ratio = -(H1 - H0);
             float logu = logu_acc[c];
-            if (!rngp) {
+            if (!rngp && !bdraw) {
                 const mc_u32x4 ru = mc_draw(cfg.seed, (uint32_t)(cfg.chain_offset + cc[c]),
                                             (uint32_t)it, MC_RNG_TAG_ACCEPT, 0, 0);
                 logu = mc_logf_u01(mc_u01_f32(ru.x));

@@ -268,7 +268,18 @@ static void plan_hmc_dense(mc_program* p) {
     const bool ok = plan_slices(p, DS, P, part) == MC_OK && plan_lanes(p, part, L) == MC_OK &&
                     L.fast && L.form == HIER && L.rep == 1 && L.S == DS && !L.has_xf &&
                     (DS == 1 || L.rs == 2) && upload_lanes(L) == hipSuccess;
-    if (!ok) free_lanes(L);
+    if (!ok) {
+        free_lanes(L);
+        return;
+    }
+    // Without a lane RNG plan (plan_lanes.hip plan_lane_rng: a slice with more
+    // than 62 (chain, block) jobs — 124 private parameters: every 8 x 2 plan)
+    // the workgroup draws each Philox block once and hands the normals out
+    // through LDS (lanes_fast.h draw_block) instead of every lane drawing a
+    // block per normal it needs.  (Of the one-wave kernels the four-slot one
+    // alone: lanes_fast.h BDRAW.)  MC_HMC_DENSE_RNG=0 keeps the per-lane draws
+    // (A/B; the draws are the same bits either way).
+    L.blk_rng = L.rng.empty() && (DS > 1 || L.rs == 4) && env_on("MC_HMC_DENSE_RNG");
 }
 
 static int set_slices(mc_program* p, int32_t S);
@@ -294,6 +305,17 @@ extern "C" int32_t mc_program_hmc_dense(const mc_program* p, int32_t* slices, in
     if (slices) *slices = on ? p->lrd.S : 0;
     if (slots) *slots = on ? p->lrd.rs : 0;
     return on ? 1 : 0;
+}
+
+// Test hook: how the dense HMC route draws.  0: HMC launches run the
+// program-level plan; 1: the dense plan has a lane RNG plan; 2: it has none
+// and the workgroup draws block-wide; 3: none, per-lane draws
+// (MC_HMC_DENSE_RNG=0).  -1 on a null program.
+extern "C" int32_t mc_debug_hmc_dense_rng(const mc_program* p) {
+    if (!p) return -1;
+    if (!hmc_dense_route(p)) return 0;
+    if (!p->lrd.rng.empty()) return 1;
+    return p->lrd.blk_rng ? 2 : 3;
 }
 
 // Test hook: the moment constants (c, R, Q, n) of the program-level lane plan

@@ -98,8 +98,12 @@ inline int launch_hmc_dense(const mc_program* p, const mc_run_config* cfg, void*
     ws_forget(ws);  // (no status word: mc_workspace_status has nothing to read)
     const int64_t groups = (cfg->num_chains + 1) / 2;
     const size_t sterm_bytes = L.sterms.size() * sizeof(LrSterm);
+    // block-wide draws (LrCtx::blk_rng): per iteration parity both chains'
+    // normals, 4 per Philox block, and the two accept logs (padded to a float4)
+    const size_t draw_bytes = L.blk_rng ? (size_t)2 * (8 * ((p->D + 3) / 4) + 4) * 4 : 0;
     auto go = [&](auto kern, int waves) {
-        const size_t lds = sterm_bytes + (waves > 1 ? (size_t)2 * waves * 16 * 4 : 0);
+        const size_t lds =
+            sterm_bytes + draw_bytes + (waves > 1 ? (size_t)2 * waves * 16 * 4 : 0);
         hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(64 * waves), lds, st, ctx, R.A,
                            (int64_t)0, groups, R.scalars, R.q, R.g, samples, td,
                            (unsigned long long*)nullptr, (int*)nullptr, (uint32_t)0);
