@@ -204,7 +204,7 @@ typedef enum {
     MC_EX_BINOMIAL_LOGIT_LP = 26,  /* a = y, b = n, c = eta; n >= 0,          */
                          /* 0 <= y <= n, both integer-valued:                 */
                          /* y eta - n softplus(eta); d eta = y - n sigma(eta) */
-    MC_EX_POISSON_LOG_LP = 27      /* a = y >= 0 integer-valued, b = theta:   */
+    MC_EX_POISSON_LOG_LP = 27,     /* a = y >= 0 integer-valued, b = theta:   */
                          /* e = exp(theta); y == 0 ? -e : y theta - e;        */
                          /* d theta = y - e                                   */
     /* Outside the support: -inf, no cotangent.  A NaN eta / theta gives NaN;
@@ -213,6 +213,36 @@ typedef enum {
      * eta = -inf gives -inf for y > 0 and NaN for y = 0.  Poisson:
      * theta = -inf gives -0 for y = 0 and -inf for y > 0; theta = +inf gives
      * -inf for y = 0 and NaN for y > 0.                                      */
+    /* The two nodes of a K-class (Categorical) log mass: a log-sum-exp that
+     * chains over the K class logits, and a selection by the observed label
+     * that chains over the K classes (mlx_mcmc/distributions/categorical.py:
+     * log(p / sum p)[y], -inf for an invalid index).  Code 28 is not
+     * assigned: it stays an unknown op (MC_ERR_INVALID), as callers written
+     * against the count nodes were promised.                                 */
+    MC_EX_LOGADDEXP = 29, /* log(exp a + exp b) (mx.logaddexp), f32, one       */
+                         /* rounding per operation, with d = (a == b ? 0 :    */
+                         /* a - b):  max(a, b) + log1p(exp(-|d|));            */
+                         /* da = c sigma(d), sigma(d) = 1 / (1 + exp(-d)), and */
+                         /* db = c - da: the class cotangents of a chained    */
+                         /* softmax sum to c.  a == b (equal infinities       */
+                         /* included): a + log 2, c / 2 to each argument.  One */
+                         /* argument -inf: the other argument, which takes    */
+                         /* all of c; +inf beside anything smaller: +inf,     */
+                         /* likewise.  A NaN argument gives NaN (value and    */
+                         /* both cotangents).                                 */
+    MC_EX_PICK     = 30  /* a == k ? b : c.  a = y is the label, a CONST or   */
+                         /* DATA leaf (MC_ERR_UNSUPPORTED otherwise); the     */
+                         /* class k is the node's own constant, leaf.value    */
+                         /* (the only non-leaf node that reads its leaf       */
+                         /* field).  Nothing flows to a; the cotangent goes   */
+                         /* to the branch taken.  A NaN y takes c.            */
+    /* The log mass of label y under class logits eta_0 .. eta_{K-1} is
+     *   SUB( PICK_{K-1}(y, eta_{K-1}, ... PICK_0(y, eta_0, -inf)),
+     *        LOGADDEXP(... LOGADDEXP(eta_0, eta_1) ..., eta_{K-1}) )
+     * with one label leaf.  A label outside 0 .. K-1, or not an integer,
+     * falls through every PICK to the -inf constant: the log mass is -inf, as
+     * the reference's for an invalid index, while the log-sum side still
+     * carries its finite cotangent (-softmax) to the logits.                 */
 } mc_expr_op;
 
 /* The count distributions of mc_discrete_log_prob / mc_predictive_draw_discrete. */

@@ -47,6 +47,7 @@ MC_DIST_EXPR = 6
  MC_EX_NORMAL_LP, MC_EX_HALFNORMAL_LP, MC_EX_EXPONENTIAL_LP, MC_EX_WHERE,
  MC_EX_GAMMA_LP, MC_EX_BETA_LP, MC_EX_GT, MC_EX_GE, MC_EX_LT, MC_EX_LE,
  MC_EX_BERNOULLI_LOGIT_LP, MC_EX_BINOMIAL_LOGIT_LP, MC_EX_POISSON_LOG_LP) = range(28)
+MC_EX_LOGADDEXP, MC_EX_PICK = 29, 30   # (28 is not assigned)
 MC_EXPR_MAX_NODES = 32
 
 # mc_series_stats fields (include/mcmc355.h)

@@ -465,7 +465,8 @@ def _bshape(name: str, shapes) -> Tuple[int, ...]:
 class Expr:
     """A traced elementwise expression (MC_DIST_EXPR nodes, include/mcmc355.h
     mc_expr_node): op an MC_EX_* code, args its argument Exprs; a leaf holds
-    a parameter (view, untransformed), a data array or a constant."""
+    a parameter (view, untransformed), a data array or a constant (and an
+    MC_EX_PICK node its class, the one non-leaf node with a constant)."""
 
     __array_priority__ = 1000
 
@@ -640,7 +641,7 @@ def _index_expr(e: "Expr", item, shape) -> "Expr":
             return Expr.of(e.leaf[item])
         return e
     args = [None if a is None else _index_expr(a, item, shape) for a in e.args]
-    return Expr(e.op, args, shape=shape)
+    return Expr(e.op, args, leaf=e.leaf, shape=shape)
 
 
 def expr_term(root: Expr) -> "LogProbExpr":
@@ -751,6 +752,67 @@ def discrete_expr(name: str, value, total, arg, natural: bool) -> "LogProbExpr":
         if name != "Poisson":
             root = Expr.where(ea < 1.0, root, ninf)
         root = Expr.where(ea > 0.0, root, ninf)
+    return expr_term(root)
+
+
+def _share_data_leaves(exprs: List["Expr"]) -> List["Expr"]:
+    """The expressions with equal data arrays held by one leaf: the classes of
+    a regression each name the predictor (a1 + b1 * x, a2 + b2 * x), and one
+    leaf per array is one node and one copy in the data pool, not K."""
+    seen: Dict[tuple, Expr] = {}
+
+    def walk(e):
+        if e is None:
+            return None
+        if e.op == _lib.MC_EX_LEAF:
+            if isinstance(e.leaf, np.ndarray) and e.leaf.ndim > 0:
+                return seen.setdefault((e.leaf.shape, e.leaf.tobytes()), e)
+            return e
+        args = [walk(a) for a in e.args]
+        if all(a is b for a, b in zip(args, e.args)):
+            return e
+        return Expr(e.op, args, leaf=e.leaf, shape=e.shape)
+
+    return [walk(e) for e in exprs]
+
+
+def categorical_expr(value, entries, natural: bool) -> "LogProbExpr":
+    """Categorical log_prob with traced class arguments: entries are the K
+    class logits (natural) or probabilities, each a number, a data array, a
+    parameter (view) or an elementwise expression, scalars or one shape [N].
+    The log mass of label y is (include/mcmc355.h)
+
+        SUB( PICK_{K-1}(y, eta_{K-1}, ... PICK_0(y, eta_0, -inf)),
+             LOGADDEXP(... LOGADDEXP(eta_0, eta_1) ..., eta_{K-1}) )
+
+    K class arguments, K PICK and K - 1 LOGADDEXP nodes, the label leaf, the
+    -inf constant and the difference: 3K + 2 nodes over scalar classes, one
+    label array in the data pool (and one leaf per predictor array, however
+    many classes name it).  A label outside 0 .. K-1 (or not an
+    integer) falls through to -inf.  With probabilities eta_k = LOG(p_k) —
+    the same log-sum normalises them, the reference's p / sum p — and the
+    root sits inside where(p_k > 0, ., -inf) per class, so a point outside the
+    simplex gives -inf without a Python branch."""
+    name = "Categorical"
+    y = _concrete_f32(name, "value", value)
+    ey = Expr.of(y)
+    es = _share_data_leaves([Expr.of(e) for e in entries])
+    if not es:
+        raise TraceError(f"{name}: no classes")
+    shape = _bshape(name, [ey.shape] + [e.shape for e in es])
+    etas = es if natural else [Expr.unary(_lib.MC_EX_LOG, e) for e in es]
+    ninf = float("-inf")
+    pick = Expr.of(ninf)
+    for k, eta in enumerate(etas):
+        pick = Expr(_lib.MC_EX_PICK, [ey, eta, pick], leaf=float(k),
+                    shape=_bshape(name, [ey.shape, eta.shape, pick.shape]))
+    lse = etas[0]
+    for eta in etas[1:]:
+        lse = Expr.binary(_lib.MC_EX_LOGADDEXP, lse, eta)
+    root = Expr(_lib.MC_EX_SUB, [pick, lse], shape=shape)
+    if not natural:
+        for e in reversed(es):
+            root = Expr.where(e > 0.0, root, ninf)
     return expr_term(root)
 
 
@@ -1362,7 +1424,10 @@ def _linearize(root: Expr, n: int) -> List[tuple]:
             return len(out) - 1
         ids = [visit(a) if a is not None else -1 for a in e.args]
         ids += [-1] * (3 - len(ids))
-        out.append((e.op, ids[0], ids[1], ids[2], None))
+        # (MC_EX_PICK's class travels in the node's leaf.value)
+        const = (Operand(_lib.MC_OP_NONE, value=float(e.leaf)) if e.op == _lib.MC_EX_PICK
+                 else None)
+        out.append((e.op, ids[0], ids[1], ids[2], const))
         memo[id(e)] = len(out) - 1
         return len(out) - 1
 

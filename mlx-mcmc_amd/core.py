@@ -144,6 +144,15 @@ add = _binary("add", _trace._lib.MC_EX_ADD, np.add)
 subtract = _binary("subtract", _trace._lib.MC_EX_SUB, np.subtract)
 multiply = _binary("multiply", _trace._lib.MC_EX_MUL, np.multiply)
 divide = _binary("divide", _trace._lib.MC_EX_DIV, np.divide)
+
+
+def _logaddexp32(a, b):
+    with np.errstate(invalid="ignore"):
+        return np.logaddexp(a, b).astype(np.float32)
+
+
+# mx.logaddexp: log(exp a + exp b) without overflow (the MC_EX_LOGADDEXP node)
+logaddexp = _binary("logaddexp", _trace._lib.MC_EX_LOGADDEXP, _logaddexp32)
 std = _concrete("std", np.std)
 var = _concrete("var", np.var)
 median = _concrete("median", np.median)

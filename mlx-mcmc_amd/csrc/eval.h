@@ -1003,8 +1003,28 @@ MC_DEV float ex_poisson_lp(float y, float theta) {
     return (y == 0.0f) ? -e : y * theta - e;
 }
 
+// The two nodes of a K-class log mass (include/mcmc355.h MC_EX_LOGADDEXP /
+// MC_EX_PICK; _trace.py categorical_expr chains them).
+//   logaddexp(a, b) = max(a, b) + log1p(exp(-|d|)), d = (a == b ? 0 : a - b):
+//   no overflow (the naive log(exp a + exp b) is inf from a ~ 88), one
+//   rounding per operation.  d is 0 for equal arguments so that equal
+//   infinities (inf - inf = NaN) give a + log 2 and sigma(d) = 1/2.
+//   The cotangents are c sigma(d) and c - c sigma(d): they sum to c exactly
+//   where the subtraction is exact, so a chained softmax's class cotangents
+//   sum to the incoming one.  An argument of -inf (exp(-inf) = 0, sigma = 0
+//   or 1) returns the other and leaves it the whole cotangent; +inf beside a
+//   smaller argument likewise.  NaN propagates through d (fmaxf alone would
+//   drop it) to the value and both cotangents.
+//   pick(y, k, b, c) = y == k ? b : c: a NaN label compares false and takes c.
+MC_DEV float ex_lae_diff(float a, float b) { return a == b ? 0.0f : a - b; }
+MC_DEV float ex_logaddexp(float a, float b) {
+    const float d = ex_lae_diff(a, b);
+    return __builtin_fmaxf(a, b) + ex_log1p(ex_exp(-__builtin_fabsf(d)));
+}
+
 // Forward value of a non-leaf node (x, y, z: its argument values; c0: the
-// distribution nodes' f32 normaliser, as elem_normal / elem_halfnormal).
+// distribution nodes' f32 normaliser, as elem_normal / elem_halfnormal, or
+// MC_EX_PICK's class).
 // Divisions go through ex_div, exp / log / log1p through ex_exp / ex_log /
 // ex_log1p; sqrt / pow / tanh are ocml's.
 MC_DEV float ex_fwd(int op, float x, float y, float z, float c0) {
@@ -1038,6 +1058,8 @@ MC_DEV float ex_fwd(int op, float x, float y, float z, float c0) {
         case MC_EX_BERNOULLI_LOGIT_LP: return ex_bernoulli_lp(x, y);
         case MC_EX_BINOMIAL_LOGIT_LP: return ex_binomial_lp(x, y, z);
         case MC_EX_POISSON_LOG_LP: return ex_poisson_lp(x, y);
+        case MC_EX_LOGADDEXP: return ex_logaddexp(x, y);
+        case MC_EX_PICK: return x == c0 ? y : z;
         default: return 0.0f;
     }
 }
@@ -1109,6 +1131,14 @@ MC_DEV void ex_bwd(int op, float x, float y, float z, float v, float c, float c0
             break;
         case MC_EX_POISSON_LOG_LP:
             if (ex_is_count(x)) dy = c * (x - ex_exp(y));
+            break;
+        case MC_EX_LOGADDEXP:
+            dx = c * ex_sigmoid(ex_lae_diff(x, y));
+            dy = c - dx;
+            break;
+        case MC_EX_PICK:  // nothing to the label
+            if (x == c0) dy = c;
+            else dz = c;
             break;
         default: break;
     }
@@ -1199,6 +1229,25 @@ MC_DEV exf2 ex2_poisson_vjp(exf2 c, exf2 y, exf2 theta) {
     return exf2{ex_is_count(y.x) ? d.x : 0.0f, ex_is_count(y.y) ? d.y : 0.0f};
 }
 
+// ex_logaddexp, its cotangents and MC_EX_PICK on a pair.
+MC_DEV exf2 ex2_lae_diff(exf2 a, exf2 b) {
+    const exf2 s = a - b;
+    return exf2{a.x == b.x ? 0.0f : s.x, a.y == b.y ? 0.0f : s.y};
+}
+MC_DEV exf2 ex2_logaddexp(exf2 a, exf2 b) {
+    const exf2 d = ex2_lae_diff(a, b);
+    const exf2 n = {-__builtin_fabsf(d.x), -__builtin_fabsf(d.y)};
+    const exf2 m = {__builtin_fmaxf(a.x, b.x), __builtin_fmaxf(a.y, b.y)};
+    return m + ex2_log1p(ex2_exp(n));
+}
+MC_DEV void ex2_logaddexp_vjp(exf2 c, exf2 a, exf2 b, exf2& da, exf2& db) {
+    da = c * ex2_div(exf2{1.0f, 1.0f}, 1.0f + ex2_exp(-ex2_lae_diff(a, b)));
+    db = c - da;
+}
+MC_DEV exf2 ex2_pick(exf2 y, float k, exf2 b, exf2 c) {
+    return exf2{y.x == k ? b.x : c.x, y.y == k ? b.y : c.y};
+}
+
 MC_DEV exf2 ex2_fwd(int op, exf2 x, exf2 y, exf2 z, float c0) {
     switch (op) {
         case MC_EX_ADD: return x + y;
@@ -1214,6 +1263,8 @@ MC_DEV exf2 ex2_fwd(int op, exf2 x, exf2 y, exf2 z, float c0) {
         case MC_EX_NORMAL_LP: return ex2_normal_lp(c0, x, y, z);
         case MC_EX_BERNOULLI_LOGIT_LP: return ex2_bernoulli_lp(x, y);
         case MC_EX_POISSON_LOG_LP: return ex2_poisson_lp(x, y);
+        case MC_EX_LOGADDEXP: return ex2_logaddexp(x, y);
+        case MC_EX_PICK: return ex2_pick(x, c0, y, z);
         default:  // the rest per component through the scalar path
             return exf2{ex_fwd(op, x.x, y.x, z.x, c0), ex_fwd(op, x.y, y.y, z.y, c0)};
     }
@@ -1243,6 +1294,11 @@ MC_DEV void ex2_bwd(int op, exf2 x, exf2 y, exf2 z, exf2 v, exf2 c, float c0, ex
         }
         case MC_EX_BERNOULLI_LOGIT_LP: dy = ex2_bernoulli_vjp(c, x, y); break;
         case MC_EX_POISSON_LOG_LP: dy = ex2_poisson_vjp(c, x, y); break;
+        case MC_EX_LOGADDEXP: ex2_logaddexp_vjp(c, x, y, dx, dy); break;
+        case MC_EX_PICK:
+            dy = ex2_pick(x, c0, c, exf2{0.0f, 0.0f});
+            dz = ex2_pick(x, c0, exf2{0.0f, 0.0f}, c);
+            break;
         default: {
             float ax, ay, az, bx, by, bz;
             ex_bwd(op, x.x, y.x, z.x, v.x, c.x, c0, ax, ay, az);

@@ -527,7 +527,7 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
         d.c = s.c;
         d.leaf.kind = MC_OP_NONE;
         d.leaf.slot = -1;
-        if (s.op < MC_EX_LEAF || s.op > MC_EX_POISSON_LOG_LP)
+        if (s.op < MC_EX_LEAF || s.op > MC_EX_PICK || s.op == 28)  // (28: not assigned)
             return fail(MC_ERR_INVALID, "term %d node %d: unknown op %d", t, k, s.op);
         if (s.op == MC_EX_LEAF) {
             const mc_operand& o = s.leaf;
@@ -583,11 +583,11 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
         switch (s.op) {
             case MC_EX_ADD: case MC_EX_SUB: case MC_EX_MUL: case MC_EX_DIV: case MC_EX_POW:
             case MC_EX_GT: case MC_EX_GE: case MC_EX_LT: case MC_EX_LE:
-            case MC_EX_BERNOULLI_LOGIT_LP: case MC_EX_POISSON_LOG_LP:
+            case MC_EX_BERNOULLI_LOGIT_LP: case MC_EX_POISSON_LOG_LP: case MC_EX_LOGADDEXP:
                 ub = true;
                 break;
             case MC_EX_NORMAL_LP: case MC_EX_WHERE: case MC_EX_GAMMA_LP: case MC_EX_BETA_LP:
-            case MC_EX_BINOMIAL_LOGIT_LP:
+            case MC_EX_BINOMIAL_LOGIT_LP: case MC_EX_PICK:
                 ub = uc = true;
                 break;
             case MC_EX_HALFNORMAL_LP: case MC_EX_EXPONENTIAL_LP:
@@ -620,6 +620,15 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
             if (s.op == MC_EX_BINOMIAL_LOGIT_LP && !fixed(s.b))
                 return fail(MC_ERR_UNSUPPORTED, "term %d node %d: the Binomial node's total n "
                             "must be data or a constant", t, k);
+        }
+        // MC_EX_PICK: the label y is data or a constant, the class the node's own
+        // constant (the one non-leaf node that reads its leaf field)
+        if (s.op == MC_EX_PICK) {
+            if (!(en[s.a].op == MC_EX_LEAF &&
+                  (en[s.a].leaf.kind == MC_OP_CONST || en[s.a].leaf.kind == MC_OP_DATA)))
+                return fail(MC_ERR_UNSUPPORTED, "term %d node %d: the pick node's label y must be "
+                            "data or a constant", t, k);
+            d.leaf.cval = s.leaf.value;
         }
         // the distribution nodes' f32 normalisers (elem_normal / elem_halfnormal)
         if (s.op == MC_EX_NORMAL_LP) d.leaf.cval = dist_c0(MC_DIST_NORMAL);

@@ -1,6 +1,6 @@
 """Distributions of the tape: ``Distribution``, ``Normal``, ``HalfNormal``,
-``Exponential``, ``Gamma``, ``Beta``, and the count likelihoods ``Bernoulli``,
-``Binomial``, ``Poisson``.
+``Exponential``, ``Gamma``, ``Beta``, the count likelihoods ``Bernoulli``,
+``Binomial``, ``Poisson``, and ``Categorical``.
 
 Same constructor arguments, ``log_prob(value)`` / ``sample(key, shape)``
 contract and formulas as the reference (mlx_mcmc/distributions/base.py:6-54,
@@ -27,6 +27,13 @@ under a traced logit / log rate, with softplus(x) = max(x, 0) + log1p(exp(-|x|))
   (-inf outside the support; ``probs=`` / ``rate=`` go through eta = logit p /
   theta = log r and give -inf for p outside (0, 1) / r <= 0; the value and
   total_count are data, never traced)
+
+``Categorical(probs= / logits=)`` (mlx_mcmc/distributions/categorical.py) is the
+log mass of a label y in 0 .. K-1 under K class arguments:
+
+  log p(y) = eta_y - log sum_k exp(eta_k),  eta_k the logits or log(p_k)
+  (-inf for a label outside 0 .. K-1; traced, two chained expression nodes —
+  a selection by the label and a pairwise log-sum-exp; see the class)
 
 Inside a traced ``log_prob(params)`` (any argument is a traced parameter),
 ``log_prob`` records a fused term for the HIP tape (see _trace.py).  On
@@ -442,5 +449,120 @@ class Poisson(_Discrete):
         return f"Poisson({k}={_scalar_repr(v)})"
 
 
+class Categorical(Distribution):
+    """Categorical(probs=None, logits=None): a label y in {0 .. K-1}
+    (mlx_mcmc/distributions/categorical.py).  Exactly one of the two.
+
+    The K class arguments are
+      * a concrete array [K];
+      * a traced 1-D parameter (or expression) of K elements — K scalar class
+        arguments, the reference's meaning (num_categories = shape[0]);
+      * a Python sequence of K entries, each a number, a data array [N] or a
+        traced scalar / [N] expression — per-observation logits such as
+        ``[0.0, a1 + b1 * x, a2 + b2 * x]``.  Entries are scalars or share one
+        shape.
+
+    ``log_prob(value)`` with a traced argument records one expression term of
+    3K + 2 nodes over scalar classes (_trace.categorical_expr); value is data
+    or a constant.  A term holds at most 32 nodes: K <= 10 scalar classes,
+    K <= 4 classes with one predictor each (a_k + b_k x: 6K + 3 nodes), K = 3
+    with two predictors each (9K + 4).  A reference class (a constant 0 entry)
+    saves its predictor's nodes.  ``probs=`` normalises by the same log-sum
+    (the reference's p / sum p) and gives -inf where some p_k <= 0.
+
+    On concrete arguments ``log_prob`` is a float32 NumPy array: ``probs=``
+    as the reference — a lookup in log(p / sum p), -inf for an invalid index;
+    ``logits=`` the normalised log-softmax.  This departs from the reference
+    on purpose: its ``logits=`` path returns the un-normalised logits
+    (categorical.py:59-65, 88), which is not a log mass."""
+
+    def __init__(self, probs=None, logits=None):
+        if probs is None and logits is None:
+            raise ValueError("Categorical takes one of probs= / logits= (got neither)")
+        if probs is not None and logits is not None:
+            raise ValueError("Categorical takes one of probs= / logits= (got both)")
+        self._natural = logits is not None
+        arg = logits if self._natural else probs
+        self._entries = self._classes(arg)
+        self._traced = _trace.is_symbolic(*self._entries)
+        self.num_categories = len(self._entries)
+        if self._traced:
+            self.probs, self.logits = probs, logits
+            return
+        stacked = np.stack([np.asarray(e, np.float32) for e in
+                            np.broadcast_arrays(*[_to_f32(e) for e in self._entries])], axis=-1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if self._natural:
+                z = stacked - np.max(stacked, axis=-1, keepdims=True)
+                lse = np.log(np.sum(np.exp(z), axis=-1, keepdims=True, dtype=np.float32))
+                self.logits = (z - lse).astype(np.float32)
+                self.probs = np.exp(self.logits).astype(np.float32)
+            else:
+                self.probs = (stacked / np.sum(stacked, axis=-1, keepdims=True,
+                                               dtype=np.float32)).astype(np.float32)
+                self.logits = np.log(self.probs).astype(np.float32)
+
+    @staticmethod
+    def _classes(arg):
+        """The K class arguments as a list."""
+        if isinstance(arg, (_trace.Param, _trace.Affine, _trace.Expr)):
+            shape = tuple(_trace.Expr.of(arg).shape)
+            if len(shape) != 1:
+                raise _trace.TraceError("Categorical: a traced class argument is a 1-D parameter "
+                                        f"of K elements (got shape {shape}); per-observation "
+                                        "classes are a sequence of K entries")
+            return [arg[k] for k in range(shape[0])]
+        if isinstance(arg, (list, tuple)) and _trace.is_symbolic(*arg):
+            return list(arg)
+        if isinstance(arg, (list, tuple)) and any(np.ndim(_trace._to_numpy(e)) > 0 for e in arg):
+            return list(arg)
+        a = _to_f32(arg)
+        if a.ndim != 1:
+            raise ValueError(f"Categorical: the class argument is a 1-D array (got shape {a.shape})")
+        return [a[k] for k in range(a.shape[0])]
+
+    def log_prob(self, value):
+        if self._traced or _trace.is_symbolic(value):
+            return _trace.categorical_expr(value, self._entries, self._natural)
+        v = np.asarray(_trace._to_numpy(value))
+        # (the reference casts the value to int32; a non-integer label is invalid
+        # here, as on the device)
+        vf = v.astype(np.float64)
+        ok = (vf >= 0) & (vf < self.num_categories) & (vf == np.floor(vf))
+        idx = np.where(ok, vf, 0).astype(np.int64)
+        table = self.logits
+        if table.ndim == 1:
+            lp = table[idx]
+        else:
+            shape = np.broadcast_shapes(table.shape[:-1], idx.shape)
+            lp = np.take_along_axis(np.broadcast_to(table, shape + table.shape[-1:]),
+                                    np.broadcast_to(idx, shape)[..., None], axis=-1)[..., 0]
+        return np.where(ok, lp, -np.inf).astype(np.float32)
+
+    def _concrete_probs(self, what):
+        if self._traced or self.probs.ndim != 1:
+            raise ValueError(f"Categorical.{what} needs one concrete probability vector [K]")
+        return self.probs
+
+    def sample(self, key, shape=()):
+        """The reference's rule: the number of cumulative probabilities that a
+        uniform exceeds, on the engine's Philox uniforms."""
+        cum = np.cumsum(self._concrete_probs("sample"), dtype=np.float32)
+        u = _gpu_uniforms(key, shape)
+        return np.sum(u[..., None] > cum, axis=-1).astype(np.int32)
+
+    def entropy(self):
+        p = self._concrete_probs("entropy")
+        with np.errstate(divide="ignore"):
+            lp = np.where(p > 0, np.log(p), np.float32(0))
+        return np.float32(-np.sum(p * lp, dtype=np.float32))
+
+    def mode(self):
+        return int(np.argmax(self._concrete_probs("mode")))
+
+    def __repr__(self):
+        return f"Categorical(num_categories={self.num_categories})"
+
+
 __all__ = ["Distribution", "Normal", "HalfNormal", "Exponential", "Gamma", "Beta", "Bernoulli",
-           "Binomial", "Poisson", "Key"]
+           "Binomial", "Poisson", "Categorical", "Key"]
