@@ -367,6 +367,18 @@ int32_t mc_program_hmc_dense(const mc_program* prog, int32_t* slices, int32_t* s
  * draws its own (MC_HMC_DENSE_RNG=0 when the plan was made).  The draws are the
  * same bits in every mode.  -1 on a null program.                              */
 int32_t mc_debug_hmc_dense_rng(const mc_program* prog);
+/* Chains per workgroup (1 | 2) of a dense HMC launch of `num_chains` chains of
+ * the program on the current device.  The 4- and 8-wave dense kernels run one
+ * chain per workgroup while the launch has at most as many chains as the
+ * device has CUs (a CU per chain; pairs would leave half of them without a
+ * wave) and a chain pair above; both give the same bytes.
+ * MC_HMC_DENSE_CHAINS=1|2 in the environment when the plan was made fixes it.
+ * 0 when HMC launches do not take the dense route or take its one-wave kernel
+ * (always a pair per wave); -1 on a null program or without a device.        */
+int32_t mc_program_hmc_dense_chains(const mc_program* prog, int64_t num_chains);
+/* Test hook: that rule as a pure function of the launch's chains, the device's
+ * CU count and the override (`forced`: 1 | 2, or 0 for none).                */
+int32_t mc_debug_hmc_dense_chains(int64_t num_chains, int32_t cus, int32_t forced);
 /* Why the program's HMC launches do not run the lane-resident kernel (e.g.
  * "lane-resident kernel: more than 4 broadcast parameters"), or "" when they
  * do or no plan was attempted; valid until the next set_slices /

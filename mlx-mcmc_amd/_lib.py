@@ -229,6 +229,9 @@ SIGNATURES = [
     ("mc_program_lane_rep", ctypes.c_int32, [_VP]),
     ("mc_program_hmc_dense", ctypes.c_int32, [_VP, _VP, _VP]),
     ("mc_debug_hmc_dense_rng", ctypes.c_int32, [_VP]),
+    ("mc_program_hmc_dense_chains", ctypes.c_int32, [_VP, ctypes.c_int64]),
+    ("mc_debug_hmc_dense_chains", ctypes.c_int32,
+     [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
     ("mc_program_lane_bundle", ctypes.c_int32, [_VP]),
     ("mc_program_kernel_note", ctypes.c_char_p, [_VP]),
     ("mc_program_nuts_lanes", ctypes.c_int32, [_VP, ctypes.c_int32]),

@@ -1546,6 +1546,17 @@ class Program:
         k = int(_lib.load().mc_debug_hmc_dense_rng(self.handle))
         return {1: "plan", 2: "block", 3: "lane"}.get(k)
 
+    def hmc_dense_chains(self, num_chains: int):
+        """Chains per workgroup (1 or 2) of a dense HMC launch of `num_chains`
+        chains on the current device (mc_program_hmc_dense_chains): one while
+        every chain gets a CU of its own, a pair above, or what
+        MC_HMC_DENSE_CHAINS fixed when the program was compiled; None when HMC
+        launches do not take the dense route or take its one-wave kernel."""
+        if self.hmc_dense is None:
+            return None
+        k = int(_lib.load().mc_program_hmc_dense_chains(self.handle, int(num_chains)))
+        return k if k in (1, 2) else None
+
     @property
     def lane_bundle(self) -> int:
         """Widest bundle of private parameters one element of a gathered

@@ -124,6 +124,8 @@ struct LanePlan {
     int rep_cap = 0;     // > 0: the planner keeps rep <= rep_cap (the dense HMC plan: 1)
     int blk_rng = 0;     // the dense HMC plan, no lane RNG plan: block-wide draws
                          // (lanes.h LrCtx::blk_rng; program.hip plan_hmc_dense)
+    int dense_chains = 0;  // the dense HMC plan: MC_HMC_DENSE_CHAINS when the plan was
+                           // made (1 | 2 chains per workgroup), else 0: hmc_dense_chains
     int has_xf = 0;      // a shared parameter is transformed, or an identity term
                          // (no NUTS lanes, no term interpreter)
     int has_expr = 0;    // LS_EXPR terms: only the JIT-compiled k_hmc_lr runs the plan
@@ -734,6 +736,15 @@ inline bool lanes_forms_enabled();
 inline bool hmc_dense_route(const mc_program* p) {
     return p->lrd.ok && p->lr.ok && p->slice_kernel != 1 && lanes_fast_enabled() &&
            lanes_forms_enabled();
+}
+
+// Chains per workgroup of a dense launch of 4 or 8 slices (lanes_fast_nc.h NC): a
+// workgroup per chain while every chain then has a CU of its own — a chain
+// pair per workgroup leaves half of those CUs without a wave — and pairs for
+// larger launches.  `forced` (1 | 2, LanePlan::dense_chains) overrides the rule.
+inline int hmc_dense_chains(int64_t num_chains, int cus, int forced) {
+    if (forced == 1 || forced == 2) return forced;
+    return num_chains <= (int64_t)cus ? 1 : 2;
 }
 
 // the fast-form kernel (lanes_fast.h) for programs that qualify, unless

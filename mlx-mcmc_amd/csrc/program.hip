@@ -280,6 +280,11 @@ static void plan_hmc_dense(mc_program* p) {
     // alone: lanes_fast.h BDRAW.)  MC_HMC_DENSE_RNG=0 keeps the per-lane draws
     // (A/B; the draws are the same bits either way).
     L.blk_rng = L.rng.empty() && (DS > 1 || L.rs == 4) && env_on("MC_HMC_DENSE_RNG");
+    // MC_HMC_DENSE_CHAINS=1|2 fixes the chains per workgroup of the 4- and
+    // 8-slice launches (host.h hmc_dense_chains; A/B, tests), read here so that
+    // programs of both routes can live in one process
+    const char* nc = std::getenv("MC_HMC_DENSE_CHAINS");
+    L.dense_chains = (nc && (nc[0] == '1' || nc[0] == '2') && nc[1] == 0) ? nc[0] - '0' : 0;
 }
 
 static int set_slices(mc_program* p, int32_t S);
@@ -316,6 +321,25 @@ extern "C" int32_t mc_debug_hmc_dense_rng(const mc_program* p) {
     if (!hmc_dense_route(p)) return 0;
     if (!p->lrd.rng.empty()) return 1;
     return p->lrd.blk_rng ? 2 : 3;
+}
+
+// The chains per workgroup (1 | 2) of a dense HMC launch of `num_chains` chains
+// of the program on the current device (host.h hmc_dense_chains, with the
+// override the plan was made under); 0 when HMC launches do not take the dense
+// route or take its one-wave kernel (a chain pair per wave); -1 on a null
+// program or without a device.
+extern "C" int32_t mc_program_hmc_dense_chains(const mc_program* p, int64_t num_chains) {
+    if (!p) return -1;
+    if (!hmc_dense_route(p) || p->lrd.S < 2) return 0;
+    if (p->lrd.dense_chains) return p->lrd.dense_chains;
+    const int cus = device_cus();
+    return cus > 0 ? hmc_dense_chains(num_chains, cus, 0) : -1;
+}
+
+// Test hook: the rule itself, a pure function of the launch's chains, the
+// device's CU count and the override (0: none).
+extern "C" int32_t mc_debug_hmc_dense_chains(int64_t num_chains, int32_t cus, int32_t forced) {
+    return hmc_dense_chains(num_chains, cus, forced);
 }
 
 // Test hook: the moment constants (c, R, Q, n) of the program-level lane plan

@@ -3,6 +3,7 @@
 // the instantiations compile in parallel.
 #pragma once
 #include "launch.h"
+#include "lanes_fast_nc.h"
 
 // The launches of kernel pair k (NW waves per workgroup; X1: one slice)
 template <int NW, bool X1, typename K>
@@ -81,10 +82,12 @@ inline int launch_hmc_lr(const mc_program* p, const mc_run_config* cfg, void* st
 }
 
 // The dense launch (mc_program::lrd; lanes_fast.h DN): one workgroup per chain
-// pair, no exchange workspace, tags, co-residency check or status word — the
-// grid is the chain pairs, however many the device holds at once.  One slice:
-// the X1 kernel (a wave per workgroup); DS slices: DS waves exchanging through
-// LDS, which by the plan's choice of DS have 2 register slots.
+// pair — or per chain (lanes_fast_nc.h k_hmc_lfc, NC = 1) while the launch has no more
+// chains than the device has CUs — no exchange workspace, tags, co-residency
+// check or status word: the grid is the pairs (chains), however many the
+// device holds at once.  One slice: the X1 kernel (a wave per workgroup, always
+// a pair); DS slices: DS waves exchanging through LDS, which by the plan's
+// choice of DS have 2 register slots.
 template <int RS>
 inline int launch_hmc_dense(const mc_program* p, const mc_run_config* cfg, void* state,
                             float* samples, const mc_trace* tr, void* ws, hipStream_t st) {
@@ -96,11 +99,15 @@ inline int launch_hmc_dense(const mc_program* p, const mc_run_config* cfg, void*
     const LrCtx ctx = lrctx_of(p, L);
     const TraceDev td = trace_of(tr);
     ws_forget(ws);  // (no status word: mc_workspace_status has nothing to read)
-    const int64_t groups = (cfg->num_chains + 1) / 2;
+    // chains per workgroup: the one-wave kernel always runs a pair; the 4- and
+    // 8-wave kernels one chain while each then has a CU (host.h hmc_dense_chains)
+    const int nc = L.S == 1 ? 2 : hmc_dense_chains(cfg->num_chains, device_cus(), L.dense_chains);
+    const int64_t groups = (cfg->num_chains + nc - 1) / nc;
     const size_t sterm_bytes = L.sterms.size() * sizeof(LrSterm);
-    // block-wide draws (LrCtx::blk_rng): per iteration parity both chains'
-    // normals, 4 per Philox block, and the two accept logs (padded to a float4)
-    const size_t draw_bytes = L.blk_rng ? (size_t)2 * (8 * ((p->D + 3) / 4) + 4) * 4 : 0;
+    // block-wide draws (LrCtx::blk_rng): per iteration parity every chain's
+    // normals, 4 per Philox block, and the accept logs (padded to a float4)
+    const size_t draw_bytes =
+        L.blk_rng ? (size_t)2 * (4 * nc * ((p->D + 3) / 4) + 4) * 4 : 0;
     auto go = [&](auto kern, int waves) {
         const size_t lds =
             sterm_bytes + draw_bytes + (waves > 1 ? (size_t)2 * waves * 16 * 4 : 0);
@@ -112,8 +119,12 @@ inline int launch_hmc_dense(const mc_program* p, const mc_run_config* cfg, void*
     };
     if (L.S == 1) return go(k_hmc_lf<RS, NSH, 1, true, HIER, false, PLAIN>, 1);
     if constexpr (RS == 2) {
-        if (L.S == 4) return go(k_hmc_lf<2, NSH, 4, false, HIER, false, PLAIN, 4>, 4);
-        if (L.S == 8) return go(k_hmc_lf<2, NSH, 8, false, HIER, false, PLAIN, 8>, 8);
+        if (L.S == 4)
+            return nc == 1 ? go(k_hmc_lfc<2, NSH, 4, false, HIER, false, PLAIN, 4, 1>, 4)
+                           : go(k_hmc_lf<2, NSH, 4, false, HIER, false, PLAIN, 4>, 4);
+        if (L.S == 8)
+            return nc == 1 ? go(k_hmc_lfc<2, NSH, 8, false, HIER, false, PLAIN, 8, 1>, 8)
+                           : go(k_hmc_lf<2, NSH, 8, false, HIER, false, PLAIN, 8>, 8);
     }
     return fail(MC_ERR_UNSUPPORTED, "dense HMC: no kernel for %d slices at %d slots", L.S, RS);
 }

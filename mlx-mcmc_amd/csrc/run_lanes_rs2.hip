@@ -12,7 +12,7 @@ int hmc_dense_rs2(const mc_program* p, const mc_run_config* cfg, void* state, fl
 }
 
 #ifdef MC_STAMPS
-#if 2 == 1
-MC_STAMPS_EXPORT(mc_debug_stamps_lanes, mc_debug_stamps_lanes_wg)
-#endif
+// the two-slot unit's accumulators: the dense 4 x 2 / 8 x 2 kernels (Large)
+// and medium's one-wave kernel (scripts/stamps_lf.py)
+MC_STAMPS_EXPORT(mc_debug_stamps_lanes2, mc_debug_stamps_lanes2_wg)
 #endif

@@ -259,6 +259,9 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
     if algorithm == "hmc" and not use_metric and program.hmc_dense:
         # (slices, slots) of the dense route: a chain pair per workgroup
         info.extra["hmc_dense"] = program.hmc_dense
+        nc = program.hmc_dense_chains(C)
+        if nc is not None:  # chains per workgroup of the 4- / 8-wave kernels
+            info.extra["hmc_dense_chains"] = nc
     if use_metric and not metric_lanes:
         info.extra["kernel_note"] = ("a mass matrix runs on the chain-per-workgroup tape kernel "
                                      f"(k_{algorithm}), as num_slices=1 does")

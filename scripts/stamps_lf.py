@@ -16,7 +16,6 @@ from mlx_mcmc_amd import _lib  # noqa: E402
 
 _lib.LIB_PATH = os.path.join(ROOT, "scripts", os.environ.get("STAMPS_LIB", "libmcmc355_stamps.so"))
 lib = _lib.load()
-lib.mc_debug_stamps_lanes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -31,6 +30,13 @@ fn, init = W.hierarchical(W.ns_product(), G, N)
 prog = _trace.compile_model(fn, init)
 print(f"shape={SHAPE} slices={prog.num_slices} kernel={prog.slice_kernel} fast={prog.lanes_fast} "
       f"chains={C}")
+# the accumulators of the unit that holds the kernel: the two-slot unit for the
+# dense 4 x 2 / 8 x 2 launches and medium, else the one-slot unit
+two = prog.hmc_dense is not None and prog.hmc_dense[1] == 2
+stamps = lib.mc_debug_stamps_lanes2 if two else lib.mc_debug_stamps_lanes
+stamps_wg = lib.mc_debug_stamps_lanes2_wg if two else lib.mc_debug_stamps_lanes_wg
+stamps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+print(f"hmc_dense={prog.hmc_dense} stamps of the {'two' if two else 'one'}-slot unit")
 cs = _engine.ChainSet(prog, C, prog.layout.flatten(init), 2e-3)
 L = 20
 cfg = dict(chain_offset=0, num_warmup=0, num_samples=10, sample_begin=0, sample_capacity=0,
@@ -41,7 +47,7 @@ for i in range(40):
     cs.run_hmc(iter_begin=i * 10, iter_count=10, **cfg)
 torch.cuda.synchronize()
 cs.check_status()
-lib.mc_debug_stamps_lanes(None, None, 1)
+stamps(None, None, 1)
 t = time.perf_counter()
 cs.run_hmc(iter_begin=400, iter_count=ITERS, **cfg)
 torch.cuda.synchronize()
@@ -49,11 +55,11 @@ dt = time.perf_counter() - t
 cs.check_status()
 acc = (ctypes.c_ulonglong * (16 * 32))()
 cnt = (ctypes.c_ulonglong * (16 * 32))()
-lib.mc_debug_stamps_lanes(acc, cnt, 0)
+stamps(acc, cnt, 0)
 a = np.array(acc[:], dtype=np.float64).reshape(16, 32)
 c = np.array(cnt[:], dtype=np.float64).reshape(16, 32)
 steps = max(c[0, 1], 1)
-nw = 8 if prog.num_slices > 8 else (4 if prog.num_slices > 1 else 1)
+nw = prog.hmc_dense[0] if prog.hmc_dense else (8 if prog.num_slices > 8 else (4 if prog.num_slices > 1 else 1))
 print(f"{ITERS} iterations in {dt * 1e3:.3f} ms ({dt / (ITERS * L) * 1e6:.3f} us/step incl. launch)")
 SECS = [(5, "momentum (per step)"), (0, "first sweep / loop"), (1, "finish + direct"),
         (2, "reduce-scatter + publish"), (8, "drift + sweep"), (7, "first poll round trip"),
@@ -68,8 +74,8 @@ print(f"  {'total':28s} " + " ".join(f"{x:7.0f}" for x in tot))
 print(f"  ticks per us (total / measured step incl. launch): "
       f"{tot.mean() / (dt / (ITERS * L) * 1e6):.0f}")
 wg = (ctypes.c_ulonglong * (1024 * 16))()
-lib.mc_debug_stamps_lanes_wg.argtypes = [ctypes.c_void_p]
-lib.mc_debug_stamps_lanes_wg(wg)
+stamps_wg.argtypes = [ctypes.c_void_p]
+stamps_wg(wg)
 wga = np.array(wg[:], dtype=np.float64).reshape(1024, 16) / steps
 S = prog.num_slices
 if S > 1:
