@@ -42,12 +42,127 @@ MC_DEV lf_vec<NC> lf_bc(float x) {
 }
 template <class V>
 MC_DEV V lf_fma(V a, V b, V c) { return __builtin_elementwise_fma(a, b, c); }
+
+// ---- one chain per wave: four values per step, one register, one float ----
+// A chain's step has four wave totals to exchange: value 0 is log p (last step
+// only), value 1 + k the cotangent of shared slot k (NSH = 3).  lf_rs8 carries
+// them as the even pairs of eight with zeros for the partner chain; lf_rs4
+// takes the four alone and leaves value v's total in row v of ONE register.
+// Per value the summation tree is lf_rs8's: lane l + lane l + 32, then + lane
+// l + 16, then the four DPP levels inside the row — only the register and the
+// half of the wave in which a value is summed differ, and every add is of the
+// same two operands (fp add is commutative), so the totals are the same bits.
+// Z0: value 0 carries nothing (not a last step): v[0] is not read and row 0 of
+// the result is unspecified.  (The 32-lane swap that places v[2] needs a
+// partner register: a dead one, the first half of the swap before it, not a
+// zero materialised per step — lf_rs8's Z01 trick.)
+//
+// The lane maps that go with it (checked below, at compile time):
+//   lf_rs4's inputs   the 32-lane swaps pair (v[0], v[2]) and (v[1], v[3]),
+//                     the 16-lane swap joins them: row r = input 2 (r & 1) +
+//                     (r >> 1) of (v[0], v[2], v[1], v[3]) = value r;
+//   the LDS line      per parity [slice][4] floats, value v of slice s at
+//                     4 s + v, then K0[slice], K1[slice] (first / last step);
+//   the publish       lane 16 v of wave s stores value v (one ds_write_b32);
+//   the read          lane 16 r + c reads value r of slice c < DN (one
+//                     ds_read_b32; no two lanes of the 32 readers share a bank),
+//                     so after the 16-lane slice sum row r holds value r;
+//   the holders       shared slot k lives in lane 16 (k + 1): its cotangent
+//                     total is in its own register without a select.
+// The pair kernel's holders are lanes 16, 1, 17 (lf_shlane); the own priors'
+// log p must enter the log-p sum in THOSE lanes (the lane fixes the term's
+// place in the tree), so the last step hands it over (k_hmc_lfc below).
+constexpr int lfc_rs4_input(int v) { return v == 1 ? 2 : (v == 2 ? 1 : v); }  // value -> input
+constexpr int lfc_rs4_row_input(int r) { return 2 * (r & 1) + (r >> 1); }     // row -> input
+constexpr int lfc_holder(int k) { return 16 * (k + 1); }
+constexpr int lfc_line_floats(int NC, int DN) { return NC == 1 ? 6 * DN : 16 * DN; }
+constexpr int lfc_pub_off(int DN, int slice, int v) { return (void)DN, 4 * slice + v; }
+constexpr int lfc_read_off(int DN, int lane) {
+    const int row = lane >> 4, col = lane & 15;
+    return 4 * (col < DN ? col : DN - 1) + row;
+}
+constexpr bool lfc_rs4_model(int DN, int NSH) {
+    // the reduce-scatter itself, lane by lane: which input each lane holds
+    int w[2][64] = {}, t[64] = {};
+    for (int m = 0; m < 2; ++m)      // permlane32_swap(in[2m], in[2m+1]), halves added
+        for (int l = 0; l < 64; ++l) w[m][l] = 2 * m + (l >= 32 ? 1 : 0);
+    for (int l = 0; l < 64; ++l)     // permlane16_swap(w[0], w[1]), rows added
+        t[l] = w[(l >> 4) & 1][32 * (l >> 5)];
+    // every value lands in exactly one row, row v, which is the row model's
+    for (int v = 0; v < 4; ++v) {
+        int rows = 0;
+        for (int r = 0; r < 4; ++r) {
+            for (int c = 1; c < 16; ++c)
+                if (t[16 * r + c] != t[16 * r]) return false;
+            if (t[16 * r] != lfc_rs4_row_input(r)) return false;
+            if (t[16 * r] == lfc_rs4_input(v)) {
+                ++rows;
+                if (r != v) return false;
+            }
+        }
+        if (rows != 1) return false;
+    }
+    // every (slice, value) is stored by one lane of its wave, inside the value
+    // floats, and read by exactly one lane of each wave
+    for (int s = 0; s < DN; ++s)
+        for (int v = 0; v < 4; ++v) {
+            const int off = lfc_pub_off(DN, s, v);
+            if (off < 0 || off >= 4 * DN) return false;
+            int readers = 0;
+            for (int l = 0; l < 64; ++l)
+                if ((l & 15) < DN && lfc_read_off(DN, l) == off) {
+                    ++readers;
+                    if ((l >> 4) != v || (l & 15) != s) return false;
+                }
+            if (readers != 1) return false;
+        }
+    for (int l = 0; l < 64; ++l)     // (idle columns read in bounds)
+        if (lfc_read_off(DN, l) < 0 || lfc_read_off(DN, l) >= 4 * DN) return false;
+    if (4 * DN + 2 * DN != lfc_line_floats(1, DN)) return false;  // + K0[DN], K1[DN]
+    // the holders: distinct lanes, each in the row of its slot's value, none
+    // of them a lane where the pair route adds an own prior's log p twice
+    if (NSH > 3) return false;
+    for (int k = 0; k < NSH; ++k) {
+        if (lfc_holder(k) < 0 || lfc_holder(k) >= 64 || (lfc_holder(k) >> 4) != 1 + k) return false;
+        for (int k2 = 0; k2 < k; ++k2)
+            if (lfc_holder(k2) == lfc_holder(k) || lf_shlane(k2, 0) == lf_shlane(k, 0)) return false;
+    }
+    return true;
+}
+static_assert(lfc_rs4_model(8, 3) && lfc_rs4_model(4, 3) && lfc_rs4_model(2, 3) &&
+              lfc_rs4_model(16, 3), "the four-value record's lane maps");
+template <bool Z0 = false>
+MC_DEV float lf_rs4(const float (&v)[4]) {
+    // lanes 0-31: v[1] sums, lanes 32-63: v[3] sums
+    const auto r1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[1]), __float_as_uint(v[3]),
+                                                     false, false);
+    const float w1 = __uint_as_float(r1[0]) + __uint_as_float(r1[1]);
+    // lanes 0-31: v[0] sums (Z0: unspecified), lanes 32-63: v[2] sums
+    const auto r0 = __builtin_amdgcn_permlane32_swap(Z0 ? r1[0] : __float_as_uint(v[0]),
+                                                     __float_as_uint(v[2]), false, false);
+    const float w0 = __uint_as_float(r0[0]) + __uint_as_float(r0[1]);
+    // rows 0, 2: w0's halves (v[0], v[2]); rows 1, 3: w1's (v[1], v[3])
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(w0), __float_as_uint(w1),
+                                                    false, false);
+    float t = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    t += lf_dpp<0xB1>(t);
+    t += lf_dpp<0x4E>(t);
+    t += lf_dpp<0x141>(t);
+    t += lf_dpp<0x140>(t);
+    return t;
+}
+
+// the lane that holds shared slot k of chain c
+template <int NC>
+MC_DEV constexpr int lfc_shlane(int k, int c) {
+    return NC == 1 ? lfc_holder(k) : lf_shlane(k, c);
+}
 // every chain's value of shared slot k
 template <int NC>
 MC_DEV lf_vec<NC> lf_shc(float v, int k) {
     lf_vec<NC> r;
 #pragma unroll
-    for (int c = 0; c < NC; ++c) r[c] = rl(v, lf_shlane(k, c));
+    for (int c = 0; c < NC; ++c) r[c] = rl(v, lfc_shlane<NC>(k, c));
     return r;
 }
 
@@ -106,12 +221,12 @@ static_assert(lfc_draw_jobs(1000, 1) == 251 && lfc_draw_jobs_once(1000, 512, 1) 
 // compiler puts between dependent packed operations — so that a launch of at
 // most as many chains as the device has CUs uses a CU per chain where the
 // pairs leave half of them empty.  The chain's arithmetic and every summation
-// tree are the pair kernel's for that chain: it keeps the pair -> row map of
-// the records with the odd pairs (chain 1's) empty — zeros into the
-// reduce-scatter, neither published nor polled, and no lane holds a chain-1
-// shared slot — and an odd chain of the launch, chain 1 of a pair there, adds
-// its own priors' log p where that chain would (32 lanes up), so the two
-// routes' results are the same bytes.
+// tree are the pair kernel's for that chain; its record is the four values of
+// one chain (lf_rs4 above: one register, one float per slice and value in the
+// LDS line, the shared slots held in lanes 16, 32, 48), and the own priors'
+// log p is added in the pair route's lanes — for an odd chain of the launch,
+// chain 1 of a pair there, 32 lanes up — so the two routes' results are the
+// same bytes.
 template <int RS, int NSH, int NW, bool X1, int FORM, bool XL = false, int SPEC = 0, int DN = 0,
           int NC = 2>
 __global__ void __launch_bounds__(64 * NW)
@@ -166,15 +281,21 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
         cc[c] = min(cbase + b0 + (c < NC ? c : 0), C - 1);
     }
 
-    // LDS: (dense: the record lines [parity][slice][16], then) the scalar
+    // LDS: (dense: the record lines [parity][slice][16] — one chain per wave:
+    // [parity]{[slice][4], K0[slice], K1[slice]}, lf_rs4 above — then) the scalar
     // terms.  The slice block stays in global memory: a step reads no
     // observation (lf_moments), and the run lengths come with the constants.
+    constexpr bool RS4 = NC == 1;       // the four-value record (lf_rs4)
+    static_assert(!RS4 || (CF && NSH == 3 && lfc_rs4_model(DN, NSH)),
+                  "one chain per wave: log p and three cotangents");
+    constexpr int LW = lfc_line_floats(NC, DN);  // floats per parity
+    static_assert((2 * LW) % 4 == 0, "the scalar terms' float4 copies follow the lines");
     float* const xl = smem;
     const int64_t* blk = P.blocks + 4 * (int64_t)slice;
     const float* gd = P.data + blk[0];
     const int nsweep = (int)(blk[3] & 255);
     const int ndirect = (int)((blk[3] >> 8) & 255);
-    LrSterm* sst = (LrSterm*)(smem + (DENSE ? 2 * DN * 16 : 0));
+    LrSterm* sst = (LrSterm*)(smem + (DENSE ? 2 * LW : 0));
     for (int i = tid; i < P.n_sterms * (int)(sizeof(LrSterm) / 16); i += 64 * NW)
         ((float4*)sst)[i] = ((const float4*)P.sterms)[i];
 
@@ -205,7 +326,7 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
     for (int k = 0; k < kLrMaxShared; ++k)
 #pragma unroll
         for (int c = 0; c < NC; ++c)
-            if (k < nsl && lf_shlane(k, c) == j) {
+            if (k < nsl && lfc_shlane<NC>(k, c) == j) {
                 xk = k;
                 xc = c;
             }
@@ -405,7 +526,14 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
         gp[par] = DENSE ? nullptr : gline[par] + min(col, S - 1) * 16 + lf_row(row);
     // dense: the same lines in LDS, a float per pair (no tags), [parity][slice][16]
     const int lpoll = min(col, S - 1) * 16 + lf_row(row);
-    auto lput = [&](int par, int off, float v) { xl[par * (DN * 16) + off] = v; };
+    auto lput = [&](int par, int off, float v) { xl[par * LW + off] = v; };
+    // one chain per wave (lf_rs4): lane 16 v stores value v of this wave's
+    // slice; lane 1 / lane 17 the K0 / K1 float of a first / last step; lane
+    // 16 r + c reads value r of slice c, rows 0 / 1 the K0 / K1 floats
+    const int pub4_off = lfc_pub_off(DN, slice, row);
+    const bool pub4 = col == 0, pub4_mid = col == 0 && row > 0;
+    const int lrd4 = lfc_read_off(DN > 0 ? DN : 1, j);
+    const int lrdk = 4 * DN + (row & 1) * DN + min(col, S - 1);
     // publishing: lanes 16 r + n (n < NRS * 2) hold pair 8 (n / 2) + 4 (n % 2) + perm[r]
     const int pub_pair = (col < 2 * NRS) ? 8 * (col >> 1) + 4 * (col & 1) + lf_row(row) : -1;
     // (NC = 1: the odd pairs, chain 1's, are neither published nor polled)
@@ -612,7 +740,7 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
             const float p2 = sh.p * sh.p;
             for (int k = 0; k < nsl; ++k) {
 #pragma unroll
-                for (int c = 0; c < NC; ++c) k0s[c] += lf_sh(p2, k, c);
+                for (int c = 0; c < NC; ++c) k0s[c] += rl(p2, lfc_shlane<NC>(k, c));
             }
         }
         fc q0[RS], g0[RS];
@@ -638,7 +766,12 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
                 q[r] = q[r] + e * pj;
             }
         };
-        float gown = 0.0f;  // the own prior's gradient at sh.v
+        // The own prior's gradient at sh.v.  A pair: formed with sh.v, below.
+        // One chain per wave: formed by the step that adds it, behind its LDS
+        // read — off the chain reciprocal -> broadcast -> next finish that
+        // drift_shared heads (profiles/lf_rs4; the same expression on the
+        // same operand either way).
+        float gown = 0.0f;
         auto drift_shared = [&](bool second_half) {
             const float hg = xh * sh.g;
             float pj = sh.p;
@@ -655,7 +788,7 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
             // is taken on the last step only, where log p is formed.
             sh.is = __builtin_amdgcn_rcpf(sh.v);
             sh.iv = sh.is * sh.is;
-            gown = vpin(own_grad(sh.v));  // for the step at this position
+            if constexpr (!RS4) gown = vpin(own_grad(sh.v));  // for the step at this position
         };
         drift_private(false);
         drift_shared(false);
@@ -804,7 +937,7 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
             // the own prior of this lane's shared parameter (moment form with
             // the constant scale's reciprocals, as the sliced terms); its log p
             // enters slice 0's record
-            const float g_own = gown;  // (formed with sh.v, in drift_shared)
+            float g_own = gown;  // (a pair: formed in drift_shared; one chain: below)
             {
                 if (lst) {
                     const float v = sh.v;
@@ -817,19 +950,28 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
                         if (own_lp0) lpp[0] += lp_own;
                         if (own_lp1) lpp[1] += lp_own;
                     } else {
-                        // An odd chain of the launch is chain 1 of its pair on
-                        // the pair route, where its own priors enter the log-p
-                        // sum in the lanes lf_shlane(k, 1), 32 above this
-                        // route's holders: handed up there (last step only),
-                        // the wave total is summed in the pair route's order.
+                        // On the pair route the own priors enter the log-p sum
+                        // in the holders' lanes lf_shlane(k, 0) (16, 1, 17) —
+                        // for an odd chain of the launch, chain 1 of its pair
+                        // there, in lf_shlane(k, 1), 32 above — and the lane
+                        // fixes a term's place in the summation tree.
                         static_assert(lf_shlane(0, 1) == lf_shlane(0, 0) + 32 &&
                                       lf_shlane(1, 1) == lf_shlane(1, 0) + 32 &&
                                       lf_shlane(2, 1) == lf_shlane(2, 0) + 32 &&
                                       lf_shlane(3, 1) == lf_shlane(3, 0) + 32, "chain 1's holders");
+                        // This route's holders are the lanes lfc_holder(k) (the
+                        // rows of lf_rs4's totals): each hands its term to the
+                        // pair route's lane of its slot and chain, so the wave
+                        // total is summed in the pair route's order.
                         const bool odd = (cbase & 1) != 0;
-                        const float lp_up = __shfl_xor(own_lp0 ? lp_own : 0.0f, 32);
-                        const bool on_up = __shfl_xor(own_lp0 ? 1 : 0, 32) != 0;
-                        if (odd ? on_up : own_lp0) lpp[0] += odd ? lp_up : lp_own;
+                        const float lpo = own_lp0 ? lp_own : 0.0f;
+#pragma unroll
+                        for (int k = 0; k < NSH; ++k) {
+                            const float lpk = rl(lpo, lfc_holder(k));
+                            const bool onk =
+                                __builtin_amdgcn_readlane(own_lp0 ? 1 : 0, lfc_holder(k)) != 0;
+                            if (onk && j == lf_shlane(k, 0) + (odd ? 32 : 0)) lpp[0] += lpk;
+                        }
                     }
                     // the identity terms over the raw parameter (log-Jacobians)
                     if (hxf && slice == 0 && xon) {
@@ -841,7 +983,17 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
             MC_STAMP(1);
             // wave totals, reduce-scattered: pair P = 2 slot + chain
             float xr[2 * NRS];
-            {
+            float xr4 = 0.0f;  // one chain per wave: value v's total in row v
+            if constexpr (RS4) {
+                float v[4];
+                v[0] = lpp[0];
+                v[1 + lf_slot_sws(FORM)] = (FORM & LF_SWS) ? cs[0] : 0.0f;
+                v[1 + lf_slot_dm(FORM)] = (FORM & LF_DM) ? cm[0] : 0.0f;
+                v[1 + lf_slot_ds(FORM)] = (FORM & LF_DS) ? cd[0] : 0.0f;
+                xr4 = lst ? lf_rs4(v) : lf_rs4<true>(v);  // (no log p but on the last step)
+#pragma unroll
+                for (int x = 0; x < 2 * NRS; ++x) xr[x] = 0.0f;
+            } else {
                 float v[8 * NRS];
 #pragma unroll
                 for (int x = 0; x < 8 * NRS; ++x) v[x] = 0.0f;
@@ -889,7 +1041,27 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
             }
             ++epoch;
             const int par = PAR >= 0 ? PAR : (int)(epoch & 1);
-            if constexpr (!X1 && !FIRST && !LAST) {
+            if constexpr (RS4 && !FIRST && !LAST) {
+                // an intermediate step: the three cotangents, from the one
+                // register, at addresses fixed per launch and parity
+                if (pub4_mid) lput(par, pub4_off, xr4);
+            } else if constexpr (RS4) {
+                // one store instruction: the values (log p on the last step
+                // only) and the K float of a first / last step
+                int po = (pub4 && (lst || row > 0)) ? pub4_off : -1;
+                float pv = xr4;
+                if (col == 1) {
+                    if (FIRST && row == 0) {
+                        po = 4 * DN + slice;
+                        pv = K0w[0];
+                    }
+                    if (LAST && row == 1) {
+                        po = 5 * DN + slice;
+                        pv = k1w[0];
+                    }
+                }
+                if (po >= 0) lput(par, po, pv);
+            } else if constexpr (!X1 && !FIRST && !LAST) {
                 // an intermediate step: the record pairs only (addresses and
                 // the lane's pair fixed per launch)
                 float pv = xr[0];
@@ -981,11 +1153,25 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
                 // next step's barrier, which every wave reaches only after
                 // these reads
                 __syncthreads();
+                if constexpr (RS4) {
+                    // one float per lane (a first / last step: and its K float)
+                    const float va = xl[par * LW + lrd4];
+                    const float vk = kstep ? xl[par * LW + lrdk] : 0.0f;
+                    // while the reads are on their way: the own prior's
+                    // gradient at this step's shared value
+                    g_own = own_grad(vpin(sh.v));
+                    // (idle columns enter the 16-lane slice sums as zeros)
+                    vals[0] = poll_lane ? va : 0.0f;
+                    const bool ndk = poll_lane && ((FIRST && row == 0) || (LAST && row == 1));
+                    if constexpr (NPASS > 1) vals[1] = ndk ? vk : 0.0f;
+                } else {
 #pragma unroll
-                for (int ps = 0; ps < NPASS; ++ps) {
-                    const bool nd = ((need >> ps) & 1u) != 0u;
-                    const float v = (ps < NPASS_V || kstep) ? xl[par * (DN * 16) + lpoll + 4 * ps] : 0.0f;
-                    vals[ps] = nd ? v : 0.0f;
+                    for (int ps = 0; ps < NPASS; ++ps) {
+                        const bool nd = ((need >> ps) & 1u) != 0u;
+                        const float v =
+                            (ps < NPASS_V || kstep) ? xl[par * LW + lpoll + 4 * ps] : 0.0f;
+                        vals[ps] = nd ? v : 0.0f;
+                    }
                 }
             }
             // (dense: nothing to wait for, no timeout — none of the poll, its
@@ -1018,6 +1204,19 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
             if constexpr (X1) {
 #pragma unroll
                 for (int ps = 0; ps < NPASS; ++ps) tot[ps] = ps < 2 * NRS ? xr[ps] : 0.0f;
+            } else if constexpr (RS4) {
+                // value r in row r of tot[0]; K0 / K1 in rows 0 / 1 of tot[1]
+#pragma unroll
+                for (int ps = 0; ps < NPASS; ++ps) {
+                    float t = ps < 2 ? vals[ps] : 0.0f;
+                    if (ps == 0 || (ps == 1 && kstep)) {
+                        t += lf_dpp<0xB1>(t);
+                        t += lf_dpp<0x4E>(t);
+                        t += lf_dpp<0x141>(t);
+                        t += lf_dpp<0x140>(t);
+                    }
+                    tot[ps] = t;
+                }
             } else {
 #pragma unroll
                 for (int ps = 0; ps < NPASS; ++ps) {
@@ -1038,9 +1237,13 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
             }
             {
                 float gx = 0.0f;
+                if constexpr (RS4) {
+                    gx = tot[0];  // lane 16 (k + 1) holds slot k: its own row's total
+                } else {
 #pragma unroll
-                for (int ps = 0; ps < NPASS_V; ++ps)
-                    if (col == ps) gx = tot[ps];  // lane 16 row + P / 4 holds pair P
+                    for (int ps = 0; ps < NPASS_V; ++ps)
+                        if (col == ps) gx = tot[ps];  // lane 16 row + P / 4 holds pair P
+                }
                 float gt = gx + g_own;
                 // the value's cotangent through the transform's VJP, plus the
                 // raw identity terms (eval.h xf_chain: the tape's arithmetic)
@@ -1052,6 +1255,8 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
                 if constexpr (X1) {
                     K0[0] = K0w[0];
                     K0[1] = K0w[1];
+                } else if constexpr (RS4) {
+                    K0[0] = rl(tot[1], 0);
                 } else {
                     K0[0] = rl(tot[p0 / 4], 16 * lf_row(p0));
                     if constexpr (NC == 2) K0[1] = rl(tot[p1 / 4], 16 * lf_row(p1));
@@ -1062,6 +1267,8 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
                 if constexpr (X1) {
                     K1[0] = k1w[0];
                     K1[1] = k1w[1];
+                } else if constexpr (RS4) {
+                    K1[0] = rl(tot[1], 16);
                 } else {
                     K1[0] = rl(tot[p0 / 4], 16 * lf_row(p0));
                     if constexpr (NC == 2) K1[1] = rl(tot[p1 / 4], 16 * lf_row(p1));
@@ -1122,7 +1329,7 @@ k_hmc_lfc(LrCtx P, RunArgs A, int64_t chain_base, int64_t n_groups, mc_chain_sca
             const float p2 = p1 * p1;
             for (int k = 0; k < nsl; ++k) {
 #pragma unroll
-                for (int c = 0; c < NC; ++c) k1s[c] += lf_sh(p2, k, c);
+                for (int c = 0; c < NC; ++c) k1s[c] += rl(p2, lfc_shlane<NC>(k, c));
             }
         }
         bool acc[2];

@@ -109,8 +109,9 @@ inline int launch_hmc_dense(const mc_program* p, const mc_run_config* cfg, void*
     const size_t draw_bytes =
         L.blk_rng ? (size_t)2 * (4 * nc * ((p->D + 3) / 4) + 4) * 4 : 0;
     auto go = [&](auto kern, int waves) {
-        const size_t lds =
-            sterm_bytes + draw_bytes + (waves > 1 ? (size_t)2 * waves * 16 * 4 : 0);
+        // (the record lines, per parity: lanes_fast_nc.h lfc_line_floats)
+        const size_t lds = sterm_bytes + draw_bytes +
+                           (waves > 1 ? (size_t)2 * lfc_line_floats(nc, waves) * 4 : 0);
         hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(64 * waves), lds, st, ctx, R.A,
                            (int64_t)0, groups, R.scalars, R.q, R.g, samples, td,
                            (unsigned long long*)nullptr, (int*)nullptr, (uint32_t)0);
