@@ -23,7 +23,8 @@
  *   mlx_mcmc/distributions/beta.py:37-91               MC_DIST_BETA term / mc_dist_log_prob
  *   mlx.core.random (key/split/normal/uniform)         Philox4x32-10 counter RNG, mc_rng_fill
  *   examples/06_nuts_comparison.py:22-41 compute_ess   mc_series_stats (MC_ST_ESS)
- *   README.md:214 roadmap "R-hat" (no reference code)  mc_stats_reduce + mc_rhat
+ *   README.md:214 roadmap "R-hat" (no reference code)  mc_stats_reduce + mc_rhat; rank-normalised:
+ *                                                      mc_rank_diag, mc_geyer_ess_host
  *   mlx_mcmc/inference/mcmc.py:191-227 summary         mc_pool_moments, mc_select
  *   README.md roadmap "Model comparison (WAIC, LOO)"   mc_pointwise_stats (no reference code)
  *   README.md:216 roadmap "Posterior predictive checks" mc_predictive, mc_predictive_draw
@@ -1020,6 +1021,80 @@ int64_t mc_psis_workspace_bytes(const mc_program* prog, int64_t C, int64_t S, do
 int mc_psis_loo(const mc_program* prog, int64_t C, int64_t S, double r_eff,
                 const float* samples_dev, double* out_dev, float* tail_dev,
                 void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
+/* ---- Rank-normalised split R-hat, bulk-ESS and tail-ESS (Vehtari, Gelman,
+ * Simpson, Carpenter and Buerkner 2021, Bayesian Analysis 16(2); no reference
+ * code) ---------------------------------------------------------------------
+ * For one element d of a [C, S, D] f32 buffer:
+ *   split chains   h = floor(S / 2); the halves are draws [0, h) and [S - h, S)
+ *                  of every chain (the middle draw of an odd S is dropped, as
+ *                  mc_series_stats drops it): m = 2C split chains of n = h
+ *                  draws, N = m n, position p = j n + i.  n < 4: every output
+ *                  is NaN.
+ *   pool           over the N split draws: the median as np.median of f32, q05
+ *                  and q95 as np.percentile of f32 with the 'linear' rule (the
+ *                  ranks and the weight formed in f32 on the host, the two-
+ *                  branch interpolation in f32 on the device).
+ *   ranks          r = the average rank of every value among the N (ties share
+ *                  the mean of their positions; -0 and +0 are equal; +-inf
+ *                  have ranks); z = ndtri((r - 3/8) / (N + 1/4)) in f64.
+ *   R(y), y [m, n] W = mean_j var_j (ddof 1), B/n = var_j(mean_j, ddof 1),
+ *                  var+ = (n - 1)/n W + B/n, R = sqrt(var+ / W).
+ *   ESS(y)         acov_j(t) = (1/n) sum_{i < n - t} (y_ji - mean_j)(y_j,i+t -
+ *                  mean_j), a_t = mean_j acov_j(t), W = a_0 n / (n - 1),
+ *                  rho_t = 1 - (W - a_t) / var+, rho_0 = 1; then the sequence
+ *                  rule of Stan's compute_effective_sample_size (Geyer's
+ *                  initial positive and monotone sequences over pairs):
+ *                    r[0] = even = 1; r[1] = odd = rho_1; t = 1
+ *                    while t < n - 3 and even + odd > 0:
+ *                        even = rho_{t+1}; odd = rho_{t+2}
+ *                        if even + odd >= 0: r[t+1] = even; r[t+2] = odd
+ *                        t += 2
+ *                    max_t = t - 2
+ *                    if even > 0: r[max_t + 1] = even
+ *                    for t = 1, 3, ... <= max_t - 2:
+ *                        if r[t+1] + r[t+2] > r[t-1] + r[t]:
+ *                            r[t+1] = r[t+2] = (r[t-1] + r[t]) / 2
+ *                    tau = -1 + 2 sum(r[0 .. max_t]) + r[max_t + 1]
+ *                    tau = max(tau, 1 / log10(N)); ESS = N / tau
+ *                  (entries of r never written are 0).
+ *   outputs        RHAT_BULK = R(z(y)); RHAT_FOLDED = R(z(|y - median|)), the
+ *                  difference and its absolute value in f32; RHAT_RANK the
+ *                  larger; ESS_BULK = ESS(z(y)); ESS_TAIL = min(ESS(1[y <=
+ *                  q05]), ESS(1[y <= q95])); CONSTANT = 1 where all N draws are
+ *                  equal, else 0.
+ *   edges          an element with a NaN draw: NaN in the five, CONSTANT 0.  W
+ *                  = 0 (a constant element, a constant indicator): NaN.
+ *
+ * mc_rank_diag: a launch function (asynchronous, no allocation, no
+ * synchronisation).  out_dev is [MC_RD_COUNT, D] f64.  z_dev is NULL or
+ * [D, 2C, n] f64 and receives the bulk z-scores (small problems and tests).
+ * Elements are processed in batches that share workspace_dev
+ * (mc_rank_diag_workspace_bytes(C, S, D) bytes: 28 N bytes per element of a
+ * batch plus the sort's histograms and the split-chain means); the batch size depends on (C, S, D) and
+ * a fixed cap only, never on the device.  Pairs (key, position) are sorted by a
+ * stable LSD radix sort, in one workgroup's LDS for N <= 8192, else across
+ * workgroups; counts are integers and every f64 sum has a fixed order: two
+ * calls give the same bits, on either path, with any batch size, with or
+ * without z_dev.  N >= 2^31 is MC_ERR_UNSUPPORTED.
+ *
+ * mc_geyer_ess_host: the sequence rule on the host (no device), the code the
+ * kernel runs: rho[n - 1] holds rho_1 .. rho_{n-1}, n >= 4.
+ *
+ * mc_debug_rank_path: 0 automatic; 1 the multi-workgroup sort for every N; 2
+ * batches of at most 3 elements.  Returns the previous value. */
+#define MC_RD_RHAT_BULK    0
+#define MC_RD_RHAT_FOLDED  1
+#define MC_RD_RHAT_RANK    2
+#define MC_RD_ESS_BULK     3
+#define MC_RD_ESS_TAIL     4
+#define MC_RD_CONSTANT     5
+#define MC_RD_COUNT        6
+int64_t mc_rank_diag_workspace_bytes(int64_t C, int64_t S, int64_t D);
+int mc_rank_diag(int64_t C, int64_t S, int64_t D, const float* samples_dev, double* out_dev,
+                 double* z_dev, void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+int mc_geyer_ess_host(const double* rho, int64_t n, int64_t N, double* ess);
+int mc_debug_rank_path(int path);
 
 const char* mc_last_error(void);
 int32_t mc_abi_version(void);

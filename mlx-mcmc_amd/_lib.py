@@ -67,6 +67,11 @@ MC_PP_COUNT = 5
  MC_PSIS_TAILN) = range(6)
 MC_PSIS_COUNT = 6
 
+# mc_rank_diag fields (include/mcmc355.h)
+(MC_RD_RHAT_BULK, MC_RD_RHAT_FOLDED, MC_RD_RHAT_RANK, MC_RD_ESS_BULK, MC_RD_ESS_TAIL,
+ MC_RD_CONSTANT) = range(6)
+MC_RD_COUNT = 6
+
 # mc_discrete_kind (mc_discrete_log_prob)
 MC_DISCRETE_BERNOULLI, MC_DISCRETE_BINOMIAL, MC_DISCRETE_POISSON = range(3)
 
@@ -345,6 +350,13 @@ SIGNATURES = [
     ("mc_psis_loo", ctypes.c_int,
      [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _VP, _VP, _VP, _VP, ctypes.c_int64,
       _VP]),
+    ("mc_rank_diag_workspace_bytes", ctypes.c_int64,
+     [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    ("mc_rank_diag", ctypes.c_int,
+     [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _VP, _VP, _VP, _VP, ctypes.c_int64, _VP]),
+    ("mc_geyer_ess_host", ctypes.c_int,
+     [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_double)]),
+    ("mc_debug_rank_path", ctypes.c_int, [ctypes.c_int]),
     ("mc_last_error", ctypes.c_char_p, []),
     ("mc_abi_version", ctypes.c_int32, []),
 ]

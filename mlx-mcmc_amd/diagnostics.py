@@ -38,6 +38,13 @@ values) or a handful of order statistics come back to the host.
   C x S x M replicates are stored only on request.  ``merge_predictive`` is
   the host statement of the merge.
 
+* ``rank_diagnostics(samples)`` — rank-normalised split R-hat (bulk, folded
+  and the larger of the two), bulk-ESS and tail-ESS per element (Vehtari,
+  Gelman, Simpson, Carpenter and Buerkner 2021; mc_rank_diag,
+  csrc/rankdiag.h): exact pooled average ranks from a device radix sort, a
+  multi-chain autocovariance with Geyer's truncation.  Pooled ranks need every
+  chain on one device.
+
 No CPU fallback: without the library these raise ``EngineUnavailable``
 (``merge_pointwise``, ``merge_predictive``, ``waic_from_stats`` and ``compare``
 are pure host arithmetic).
@@ -164,6 +171,54 @@ def chain_diagnostics(samples, max_lag: int = MAX_LAG, group=None) -> Dict[str, 
     return {"ess": st[_lib.MC_ST_ESS].view(C, D).cpu().numpy(),
             "ess_sum": ess_sum.cpu().numpy(), "rhat": rhat.cpu().numpy(),
             "n_constant": n_const, "n_nonpositive_ess": n_nonpos}
+
+
+RANK_FIELDS = ("rhat_bulk", "rhat_folded", "rhat_rank", "ess_bulk", "ess_tail")
+
+
+def rank_diagnostics(samples, group=None, *, z_scores=False) -> Dict[str, np.ndarray]:
+    """Rank-normalised split R-hat, bulk-ESS and tail-ESS per element of a
+    [C, S, D] buffer (Vehtari et al. 2021; the definition is stated in
+    include/mcmc355.h, mc_rank_diag).
+
+    Every chain is split in halves of n = S // 2 draws (the middle draw of an
+    odd S is dropped); the N = 2 C n split draws of an element are ranked
+    (average ranks) and mapped to normal scores z.  Returns float64 [D] arrays
+    ``rhat_bulk`` (split R-hat of z), ``rhat_folded`` (of the z of
+    |y - median|), ``rhat_rank`` (the larger), ``ess_bulk`` (Stan's ESS of z)
+    and ``ess_tail`` (the smaller ESS of the indicators y <= q05, y <= q95),
+    plus ``n_constant``, the count of constant elements.  NaN where nothing is
+    defined: S < 8, an element with a NaN draw, a constant element or
+    indicator.  ``z_scores=True`` adds ``z``, the [D, 2C, n] float64 device
+    tensor of the bulk z-scores (small problems only).
+
+    Pooled ranks need every chain's draws on one device: with an initialised
+    process group of more than one rank this raises ``ValueError`` unless
+    ``group=False`` (this rank's chains alone)."""
+    import torch
+
+    _refuse_sharded_draws(group, "rank-normalised diagnostics are not mergeable over shards of "
+                          "chains: an element's ranks are taken over every chain's draws; gather "
+                          "the chains on one rank, or pass group=False for this rank's chains "
+                          "alone")
+    x = _as_device(samples)
+    C, S, D = x.shape
+    lib = _lib.load()
+    nb = lib.mc_rank_diag_workspace_bytes(C, S, D)
+    if nb < 0:
+        _lib.check(int(nb))
+    n = S // 2
+    out = torch.empty((_lib.MC_RD_COUNT, D), dtype=torch.float64, device=x.device)
+    z = torch.empty((D, 2 * C, n), dtype=torch.float64, device=x.device) if z_scores else None
+    ws = torch.empty(max(int(nb), 8), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.mc_rank_diag(C, S, D, _lib.ptr(x), _lib.ptr(out), _lib.ptr(z), _lib.ptr(ws),
+                                nb, _lib.stream_handle()))
+    host = out.cpu().numpy()   # (synchronises: x and ws outlive the launch)
+    res = {f: host[k].copy() for k, f in enumerate(RANK_FIELDS)}
+    res["n_constant"] = int(host[_lib.MC_RD_CONSTANT].sum())
+    if z_scores:
+        res["z"] = z
+    return res
 
 
 # ------------------------------------------------------------ summary -----
@@ -453,12 +508,13 @@ def waic(log_likelihood_fn, samples, layout=None, *, group=None) -> dict:
 
 
 # ------------------------------------------------------------ PSIS-LOO -----
-def _refuse_sharded_draws(group):
+def _refuse_sharded_draws(group, why=None):
     import torch.distributed as dist
 
     if group is not False and dist.is_available() and dist.is_initialized() \
             and dist.get_world_size(group) > 1:
-        raise ValueError("PSIS-LOO is not mergeable over shards of draws: an observation's "
+        raise ValueError(why or
+                         "PSIS-LOO is not mergeable over shards of draws: an observation's "
                          "tail is taken over all draws; gather the draws on one rank, or pass "
                          "group=False for this rank's draws alone")
 

@@ -119,16 +119,20 @@ class MCMC:
             return _diag.summarize(dev, self.info.layout, credible_interval)
         return _diag.summarize(self.samples, None, credible_interval)
 
-    def diagnostics(self, max_lag=100):
+    def diagnostics(self, max_lag=100, rank_normalized=False):
         """Per parameter: ESS per chain (examples/06_nuts_comparison.py:22-41
         rule), ESS summed over chains and split R-hat, shaped like the
-        parameter (chain axis first for the per-chain ESS)."""
+        parameter (chain axis first for the per-chain ESS).
+        ``rank_normalized=True`` adds ``ess_bulk``, ``ess_tail``,
+        ``r_hat_rank``, ``r_hat_bulk`` and ``r_hat_folded`` (Vehtari et al.
+        2021; diagnostics.rank_diagnostics), shaped like the parameter."""
         if self.samples is None:
             raise ValueError("Must run sampling first. Call run() method.")
         dev = getattr(self.info, "device_samples", None)
         if dev is None:
             raise ValueError("diagnostics need the device samples (keep_on_device=True)")
         d = _diag.chain_diagnostics(dev, max_lag=max_lag, group=False)
+        rk = _diag.rank_diagnostics(dev, group=False) if rank_normalized else None
         lay = self.info.layout
         out = {}
         C = d["ess"].shape[0]
@@ -137,6 +141,11 @@ class MCMC:
             out[name] = {"ess": d["ess"][:, off:off + n].reshape((C,) + tuple(shape)),
                          "ess_sum": d["ess_sum"][off:off + n].reshape(shape),
                          "r_hat": d["rhat"][off:off + n].reshape(shape)}
+            if rk is not None:
+                for key, src in (("ess_bulk", "ess_bulk"), ("ess_tail", "ess_tail"),
+                                 ("r_hat_rank", "rhat_rank"), ("r_hat_bulk", "rhat_bulk"),
+                                 ("r_hat_folded", "rhat_folded")):
+                    out[name][key] = rk[src][off:off + n].reshape(shape)
         return out
 
     def _kept_draws(self):
