@@ -231,12 +231,31 @@ typedef enum {
                          /* all of c; +inf beside anything smaller: +inf,     */
                          /* likewise.  A NaN argument gives NaN (value and    */
                          /* both cotangents).                                 */
-    MC_EX_PICK     = 30  /* a == k ? b : c.  a = y is the label, a CONST or   */
+    MC_EX_PICK     = 30, /* a == k ? b : c.  a = y is the label, a CONST or   */
                          /* DATA leaf (MC_ERR_UNSUPPORTED otherwise); the     */
                          /* class k is the node's own constant, leaf.value    */
-                         /* (the only non-leaf node that reads its leaf       */
-                         /* field).  Nothing flows to a; the cotangent goes   */
-                         /* to the branch taken.  A NaN y takes c.            */
+                         /* (PICK and the Student-t nodes are the non-leaf    */
+                         /* nodes that read their leaf field).  Nothing flows */
+                         /* to a; the cotangent goes to the branch taken.  A  */
+                         /* NaN y takes c.                                    */
+    /* Student-t log densities (no reference code), WITHOUT the normaliser
+     * lgamma((nu + 1) / 2) - lgamma(nu / 2) - log(nu pi) / 2 (+ log 2 for the
+     * half form), which the caller adds as a CONST leaf.  The degrees of
+     * freedom nu are the node's own constant, leaf.value, finite and positive
+     * (MC_ERR_INVALID otherwise); a, b, c may be any nodes.  Code 31 is not
+     * assigned and stays an unknown op.  In f32, one rounding per operation:
+     *   d = v - m (half: d = v); z = d / s; q = z z; w = q / nu
+     *   lp = (-log s) - (nu + 1) / 2 * log1p(w)
+     *   r = z / (nu + q); g = (nu + 1) r; t = g / s
+     *   dv = -c t, dm = c t, ds = c (g z - 1) / s                            */
+    MC_EX_STUDENT_T_LP = 32,       /* a = value v, b = loc m, c = scale s     */
+    MC_EX_HALF_STUDENT_T_LP = 33   /* a = v, c = s (b unused, -1): -inf and   */
+                         /* no cotangent unless v >= 0 (a NaN v: -inf)        */
+    /* Edge classes.  q = inf (|z| beyond ~1.8e19, an infinite v or m, s = 0
+     * beside d != 0): lp = -inf (NaN for s = 0) and every cotangent 0.  A NaN
+     * v, m or s: NaN in the value and the cotangents.  s < 0: NaN; s = inf:
+     * -inf; s = 0 with d = 0: NaN — as MC_EX_NORMAL_LP.  Half form: v = -0 is
+     * inside the support.  Cauchy and half-Cauchy are nu = 1.                */
     /* The log mass of label y under class logits eta_0 .. eta_{K-1} is
      *   SUB( PICK_{K-1}(y, eta_{K-1}, ... PICK_0(y, eta_0, -inf)),
      *        LOGADDEXP(... LOGADDEXP(eta_0, eta_1) ..., eta_{K-1}) )
@@ -427,6 +446,17 @@ int mc_discrete_log_prob(int32_t kind, int64_t n,
                          const float* total_dev, int32_t total_bcast,
                          const float* eta_dev, int32_t eta_bcast,
                          float* out_dev, void* hip_stream);
+
+/* The Student-t nodes' values elementwise (the device function of
+ * MC_EX_STUDENT_T_LP / MC_EX_HALF_STUDENT_T_LP, without the normaliser):
+ * out[i] = node(value[i|0], loc[i|0], scale[i|0]) at df, finite and positive;
+ * half != 0 is the half form, which reads no loc (loc_dev may be NULL).
+ * *_bcast = 1: a single element.                                            */
+int mc_student_t_log_prob(float df, int32_t half, int64_t n,
+                          const float* value_dev, int32_t value_bcast,
+                          const float* loc_dev, int32_t loc_bcast,
+                          const float* scale_dev, int32_t scale_bcast,
+                          float* out_dev, void* hip_stream);
 
 /* ---- per-chain state ---------------------------------------------------- */
 /* State blob layout (device memory, mc_state_bytes(prog, C) bytes):
@@ -898,6 +928,15 @@ int mc_pointwise_stats(const mc_program* prog, int64_t C, int64_t S,
  *                or >= 2^23.
  * At most 32 attempts, then NaN.  An inversion's uniform resolves 2^-32:
  * outcomes beyond the 1 - 2^-33 quantile do not occur.
+ * The Student-t terms have a sampling distribution by the same rule: the root
+ * is MC_EX_STUDENT_T_LP / MC_EX_HALF_STUDENT_T_LP, or ADD of such a node and a
+ * CONST / DATA leaf.  Value, loc and scale are the node's arguments at the
+ * draw; one rule for every nu (Cauchy included), f32 IEEE operations:
+ *   z0 the first normal of mc_box_muller(w.x, w.y), attempt 0's block
+ *   g ~ Gamma(nu / 2, 1) by the Gamma sampler above on Beta's second sub range
+ *   t = z0 / sqrt(g / (nu / 2));  Student-t: loc + scale t;  half: |scale t|
+ * NaN for a scale that is <= 0 or NaN, a NaN loc, and an exhausted Gamma.
+ * For nu < 2 the Gamma shape is below 1 and its last-bit caveat applies.
  *
  * mc_predictive_draw: the scalar definition on the host (no device, no
  * allocation): *out = the replicate of observation obs under (dist, loc or
@@ -905,6 +944,9 @@ int mc_pointwise_stats(const mc_program* prog, int64_t C, int64_t S,
  *
  * mc_predictive_draw_discrete: its counterpart for the count terms (kind an
  * mc_discrete_kind, total the Binomial's n, eta the logit / log rate).
+ *
+ * mc_predictive_draw_student_t: the same for the Student-t terms (half != 0:
+ * the half form, loc unread).  df that is <= 0 or NaN gives NaN.
  *
  * mc_predictive_eq: mc_predictive plus equal_dev, NULL or [M] f64: the finite
  * replicates EQUAL to the observation (the ties a discrete PIT needs; the five
@@ -917,6 +959,8 @@ int mc_pointwise_stats(const mc_program* prog, int64_t C, int64_t S,
  *
  * mc_program_num_count_terms: how many terms of the pointwise view have a
  * count sampler (known from program creation: no device, no view needed).
+ * Student-t terms are not count terms: a program whose expression samplers are
+ * all Student-t has no ties, and its workspace is five fields per block.
  *
  * mc_predictive: samples_dev is the [C, S, D] buffer; thin >= 1 processes
  * iterations s = 0, thin, 2 thin, ... of every chain (S' = ceil(S / thin); the
@@ -941,6 +985,8 @@ int mc_predictive_draw(int dist, float loc_or_alpha, float scale_or_rate_or_beta
 int32_t mc_program_num_count_terms(const mc_program* prog);
 int mc_predictive_draw_discrete(int kind, float total, float eta, uint64_t seed,
                                 uint32_t chain, uint32_t iter, uint32_t obs, float* out);
+int mc_predictive_draw_student_t(float df, float loc, float scale, int half, uint64_t seed,
+                                 uint32_t chain, uint32_t iter, uint32_t obs, float* out);
 int64_t mc_predictive_workspace_bytes(const mc_program* prog, int64_t C, int64_t S,
                                       int64_t thin);
 int mc_predictive(const mc_program* prog, int64_t C, int64_t S, int64_t thin, uint64_t seed,

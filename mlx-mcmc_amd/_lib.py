@@ -48,6 +48,7 @@ MC_DIST_EXPR = 6
  MC_EX_GAMMA_LP, MC_EX_BETA_LP, MC_EX_GT, MC_EX_GE, MC_EX_LT, MC_EX_LE,
  MC_EX_BERNOULLI_LOGIT_LP, MC_EX_BINOMIAL_LOGIT_LP, MC_EX_POISSON_LOG_LP) = range(28)
 MC_EX_LOGADDEXP, MC_EX_PICK = 29, 30   # (28 is not assigned)
+MC_EX_STUDENT_T_LP, MC_EX_HALF_STUDENT_T_LP = 32, 33   # (31 is not assigned)
 MC_EXPR_MAX_NODES = 32
 
 # mc_series_stats fields (include/mcmc355.h)
@@ -247,6 +248,9 @@ SIGNATURES = [
     ("mc_discrete_log_prob", ctypes.c_int,
      [ctypes.c_int32, ctypes.c_int64, _VP, ctypes.c_int32, _VP, ctypes.c_int32, _VP,
       ctypes.c_int32, _VP, _VP]),
+    ("mc_student_t_log_prob", ctypes.c_int,
+     [ctypes.c_float, ctypes.c_int32, ctypes.c_int64, _VP, ctypes.c_int32, _VP, ctypes.c_int32,
+      _VP, ctypes.c_int32, _VP, _VP]),
     ("mc_state_bytes", ctypes.c_int64, [_VP, ctypes.c_int64]),
     ("mc_state_offsets", ctypes.c_int,
      [_VP, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
@@ -333,6 +337,9 @@ SIGNATURES = [
     ("mc_predictive_draw_discrete", ctypes.c_int,
      [ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32,
       ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float)]),
+    ("mc_predictive_draw_student_t", ctypes.c_int,
+     [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_uint64,
+      ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float)]),
     ("mc_predictive_workspace_bytes", ctypes.c_int64,
      [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
     ("mc_predictive", ctypes.c_int,

@@ -755,6 +755,53 @@ def discrete_expr(name: str, value, total, arg, natural: bool) -> "LogProbExpr":
     return expr_term(root)
 
 
+def student_t_df(name: str, df) -> float:
+    """The degrees of freedom of a Student-t class as a float: concrete, one
+    finite positive scalar.  A traced df raises TraceError, anything else that
+    does not qualify ValueError."""
+    if is_symbolic(df):
+        raise TraceError(f"{name}: the degrees of freedom must be a constant: a traced df needs "
+                         "an lgamma node with a digamma VJP for the normaliser "
+                         "lgamma((df + 1) / 2) - lgamma(df / 2), which the expression nodes do "
+                         "not have")
+    arr = np.asarray(_to_numpy(df))
+    if arr.dtype == object or arr.ndim != 0:
+        raise ValueError(f"{name}: df must be one scalar (got shape {arr.shape})")
+    nu = float(np.float32(arr))
+    if not (np.isfinite(nu) and nu > 0.0):
+        raise ValueError(f"{name}: df must be finite and positive (got {float(arr)})")
+    return nu
+
+
+def student_t_norm(df: float, half: bool) -> np.float32:
+    """The Student-t normaliser lgamma((nu + 1) / 2) - lgamma(nu / 2) -
+    log(nu pi) / 2 (+ log 2, half form) of the f32 nu in float64, rounded once
+    to f32."""
+    import math
+
+    nu = float(np.float32(df))
+    c = math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu) - 0.5 * math.log(nu * math.pi)
+    if half:
+        c += math.log(2.0)
+    return np.float32(c)
+
+
+def student_t_expr(name: str, df: float, value, loc, scale, half: bool) -> "LogProbExpr":
+    """StudentT / Cauchy / HalfStudentT / HalfCauchy log_prob with a traced
+    argument: ADD(MC_EX_STUDENT_T_LP | MC_EX_HALF_STUDENT_T_LP over (value[,
+    loc], scale), CONST normaliser).  df (student_t_df's float) travels in the
+    node's leaf.value, as MC_EX_PICK's class."""
+    ev, es = Expr.of(value), Expr.of(scale)
+    if half:
+        core = Expr(_lib.MC_EX_HALF_STUDENT_T_LP, [ev, None, es], leaf=float(df),
+                    shape=_bshape(name, [ev.shape, es.shape]))
+    else:
+        el = Expr.of(loc)
+        core = Expr(_lib.MC_EX_STUDENT_T_LP, [ev, el, es], leaf=float(df),
+                    shape=_bshape(name, [ev.shape, el.shape, es.shape]))
+    return expr_term(Expr.binary(_lib.MC_EX_ADD, core, float(student_t_norm(df, half))))
+
+
 def _share_data_leaves(exprs: List["Expr"]) -> List["Expr"]:
     """The expressions with equal data arrays held by one leaf: the classes of
     a regression each name the predictor (a1 + b1 * x, a2 + b2 * x), and one
@@ -1389,6 +1436,9 @@ def _build_pools(model: TracedModel) -> None:
     model.n_affines = na
 
 
+_CONST_NODE_OPS = (_lib.MC_EX_PICK, _lib.MC_EX_STUDENT_T_LP, _lib.MC_EX_HALF_STUDENT_T_LP)
+
+
 def _linearize(root: Expr, n: int) -> List[tuple]:
     """Post-order node list of an expression term (arguments before their
     users, the root last); identical leaves share one node."""
@@ -1424,8 +1474,9 @@ def _linearize(root: Expr, n: int) -> List[tuple]:
             return len(out) - 1
         ids = [visit(a) if a is not None else -1 for a in e.args]
         ids += [-1] * (3 - len(ids))
-        # (MC_EX_PICK's class travels in the node's leaf.value)
-        const = (Operand(_lib.MC_OP_NONE, value=float(e.leaf)) if e.op == _lib.MC_EX_PICK
+        # (MC_EX_PICK's class and the Student-t nodes' df travel in the node's
+        # leaf.value)
+        const = (Operand(_lib.MC_OP_NONE, value=float(e.leaf)) if e.op in _CONST_NODE_OPS
                  else None)
         out.append((e.op, ids[0], ids[1], ids[2], const))
         memo[id(e)] = len(out) - 1

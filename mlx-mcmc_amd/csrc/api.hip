@@ -122,6 +122,37 @@ extern "C" int mc_discrete_log_prob(int32_t kind, int64_t n, const float* v, int
     return MC_OK;
 }
 
+// The Student-t nodes elementwise: ex_fwd's two cases on ex_student_t_lp (the
+// function the tape calls), nu as the node constant.
+__global__ void k_student_t(float nu, int half, int64_t n, const float* v, int vb, const float* m,
+                            int mb, const float* s, int sb, float* out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const float x = v[vb ? 0 : i];
+        const float sc = s[sb ? 0 : i];
+        if (half) out[i] = x >= 0.0f ? ex_student_t_lp(nu, x, sc) : -__builtin_inff();
+        else out[i] = ex_student_t_lp(nu, x - m[mb ? 0 : i], sc);
+    }
+}
+
+extern "C" int mc_student_t_log_prob(float df, int32_t half, int64_t n, const float* v,
+                                     int32_t vb, const float* m, int32_t mb, const float* s,
+                                     int32_t sb, float* out, void* stream) {
+    if (!(df > 0.0f) || !(df < __builtin_inff()))
+        return fail(MC_ERR_INVALID, "the degrees of freedom must be finite and positive (got %g)",
+                    (double)df);
+    if (n < 0) return fail(MC_ERR_INVALID, "n < 0");
+    if (n == 0) return MC_OK;
+    const bool need_m = half == 0;
+    if (!v || !s || !out || (need_m && !m)) return fail(MC_ERR_INVALID, "NULL operand");
+    if (!need_m) mb = 1;  // the unused loc is read as element 0 of value
+    const int64_t blocks = std::min<int64_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_student_t, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, df,
+                       half != 0 ? 1 : 0, n, v, vb, need_m ? m : v, mb, s, sb, out);
+    MC_HIP_TRY(hipGetLastError());
+    return MC_OK;
+}
+
 // ---------------------------------------------------------------------------
 // state
 // ---------------------------------------------------------------------------

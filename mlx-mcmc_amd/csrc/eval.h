@@ -1022,9 +1022,52 @@ MC_DEV float ex_logaddexp(float a, float b) {
     return __builtin_fmaxf(a, b) + ex_log1p(ex_exp(-__builtin_fabsf(d)));
 }
 
+// Student-t log densities (include/mcmc355.h MC_EX_STUDENT_T_LP /
+// MC_EX_HALF_STUDENT_T_LP), without their normaliser: nu is the node's own
+// constant (c0, as MC_EX_PICK's class; program creation has checked that it is
+// finite and positive) and the normaliser lgamma((nu + 1) / 2) - lgamma(nu / 2)
+// - log(nu pi) / 2 (+ log 2, half form) is a constant leaf the tracer adds, so
+// no lgamma is compiled here and none enters a gradient.  One rounding per
+// operation:
+//   d = v - m (half form: d = v);  z = d / s;  q = z z;  w = q / nu
+//   lp = (-log s) - (nu + 1) / 2 * log1p(w)
+//   r = z / (nu + q);  g = (nu + 1) r;  t = g / s
+//   d lp / dv = -t,  d lp / dm = t,  d lp / ds = (g z - 1) / s
+// log1p keeps the bulk (w small) at full relative precision; dividing z by
+// nu + q, not d by nu s^2 + d^2, keeps the cotangents finite up to |z| ~ 2^63.
+// Edge classes (IEEE through the formulas but for the two selects named):
+//   q = inf    (|z| beyond sqrt(FLT_MAX) ~ 1.8e19, v or m infinite, s = 0 with
+//              d != 0): lp = -inf (NaN where log s is not finite: s = 0), and
+//              the cotangents are 0 by a select — the formulas would give
+//              inf / inf or the limit's wrong -1 / s
+//   NaN        a NaN v, m or s gives NaN in the value and every cotangent
+//   s < 0      NaN (log s), as MC_EX_NORMAL_LP;  s = inf: -inf
+//   s = 0, d = 0   NaN (0 / 0), as MC_EX_NORMAL_LP
+//   half form  -inf and no cotangent unless v >= 0 (ex_halfnormal's convention:
+//              a NaN v gives -inf; v = -0 is inside)
+// Between 2^63 and sqrt(FLT_MAX) in |z| the divisor nu + q is beyond ex_div's
+// range (2^126) and r comes out 0: the cotangents are then 0, 0 and -1 / s.
+MC_DEV float ex_student_t_lp(float nu, float d, float s) {
+    const float z = ex_div(d, s);
+    const float q = z * z;
+    const float w = ex_div(q, nu);
+    const float h = 0.5f * (nu + 1.0f);
+    return (-ex_log(s)) - h * ex_log1p(w);
+}
+// (gd: the factor of -dv = dm; gs: that of ds)
+MC_DEV void ex_student_t_grad(float nu, float d, float s, float& gd, float& gs) {
+    const float z = ex_div(d, s);
+    const float q = z * z;
+    const float r = ex_div(z, nu + q);
+    const float g = (nu + 1.0f) * r;
+    const bool far = q == __builtin_inff();
+    gd = far ? 0.0f : ex_div(g, s);
+    gs = far ? 0.0f : ex_div(g * z - 1.0f, s);
+}
+
 // Forward value of a non-leaf node (x, y, z: its argument values; c0: the
-// distribution nodes' f32 normaliser, as elem_normal / elem_halfnormal, or
-// MC_EX_PICK's class).
+// distribution nodes' f32 normaliser, as elem_normal / elem_halfnormal,
+// MC_EX_PICK's class or the Student-t nodes' nu).
 // Divisions go through ex_div, exp / log / log1p through ex_exp / ex_log /
 // ex_log1p; sqrt / pow / tanh are ocml's.
 MC_DEV float ex_fwd(int op, float x, float y, float z, float c0) {
@@ -1060,6 +1103,9 @@ MC_DEV float ex_fwd(int op, float x, float y, float z, float c0) {
         case MC_EX_POISSON_LOG_LP: return ex_poisson_lp(x, y);
         case MC_EX_LOGADDEXP: return ex_logaddexp(x, y);
         case MC_EX_PICK: return x == c0 ? y : z;
+        case MC_EX_STUDENT_T_LP: return ex_student_t_lp(c0, x - y, z);
+        case MC_EX_HALF_STUDENT_T_LP:
+            return x >= 0.0f ? ex_student_t_lp(c0, x, z) : -__builtin_inff();
         default: return 0.0f;
     }
 }
@@ -1139,6 +1185,22 @@ MC_DEV void ex_bwd(int op, float x, float y, float z, float v, float c, float c0
         case MC_EX_PICK:  // nothing to the label
             if (x == c0) dy = c;
             else dz = c;
+            break;
+        case MC_EX_STUDENT_T_LP: {
+            float gd, gs;
+            ex_student_t_grad(c0, x - y, z, gd, gs);
+            dx = -(c * gd);
+            dy = c * gd;
+            dz = c * gs;
+            break;
+        }
+        case MC_EX_HALF_STUDENT_T_LP:
+            if (x >= 0.0f) {
+                float gd, gs;
+                ex_student_t_grad(c0, x, z, gd, gs);
+                dx = -(c * gd);
+                dz = c * gs;
+            }
             break;
         default: break;
     }
@@ -1248,6 +1310,26 @@ MC_DEV exf2 ex2_pick(exf2 y, float k, exf2 b, exf2 c) {
     return exf2{y.x == k ? b.x : c.x, y.y == k ? b.y : c.y};
 }
 
+// ex_student_t_lp / ex_student_t_grad on a pair (nu is uniform).
+MC_DEV exf2 ex2_student_t_lp(float nu, exf2 d, exf2 s) {
+    const exf2 z = ex2_div(d, s);
+    const exf2 q = z * z;
+    const exf2 w = ex2_div(q, exf2{nu, nu});
+    const float h = 0.5f * (nu + 1.0f);
+    return (-ex2_log(s)) - h * ex2_log1p(w);
+}
+MC_DEV void ex2_student_t_grad(float nu, exf2 d, exf2 s, exf2& gd, exf2& gs) {
+    const exf2 z = ex2_div(d, s);
+    const exf2 q = z * z;
+    const exf2 r = ex2_div(z, nu + q);
+    const exf2 g = (nu + 1.0f) * r;
+    const exf2 t = ex2_div(g, s);
+    const exf2 u = ex2_div(g * z - 1.0f, s);
+    const bool fx = q.x == __builtin_inff(), fy = q.y == __builtin_inff();
+    gd = exf2{fx ? 0.0f : t.x, fy ? 0.0f : t.y};
+    gs = exf2{fx ? 0.0f : u.x, fy ? 0.0f : u.y};
+}
+
 MC_DEV exf2 ex2_fwd(int op, exf2 x, exf2 y, exf2 z, float c0) {
     switch (op) {
         case MC_EX_ADD: return x + y;
@@ -1265,6 +1347,12 @@ MC_DEV exf2 ex2_fwd(int op, exf2 x, exf2 y, exf2 z, float c0) {
         case MC_EX_POISSON_LOG_LP: return ex2_poisson_lp(x, y);
         case MC_EX_LOGADDEXP: return ex2_logaddexp(x, y);
         case MC_EX_PICK: return ex2_pick(x, c0, y, z);
+        case MC_EX_STUDENT_T_LP: return ex2_student_t_lp(c0, x - y, z);
+        case MC_EX_HALF_STUDENT_T_LP: {
+            const exf2 r = ex2_student_t_lp(c0, x, z);
+            return exf2{x.x >= 0.0f ? r.x : -__builtin_inff(),
+                        x.y >= 0.0f ? r.y : -__builtin_inff()};
+        }
         default:  // the rest per component through the scalar path
             return exf2{ex_fwd(op, x.x, y.x, z.x, c0), ex_fwd(op, x.y, y.y, z.y, c0)};
     }
@@ -1299,6 +1387,22 @@ MC_DEV void ex2_bwd(int op, exf2 x, exf2 y, exf2 z, exf2 v, exf2 c, float c0, ex
             dy = ex2_pick(x, c0, c, exf2{0.0f, 0.0f});
             dz = ex2_pick(x, c0, exf2{0.0f, 0.0f}, c);
             break;
+        case MC_EX_STUDENT_T_LP: {
+            exf2 gd, gs;
+            ex2_student_t_grad(c0, x - y, z, gd, gs);
+            dx = -(c * gd);
+            dy = c * gd;
+            dz = c * gs;
+            break;
+        }
+        case MC_EX_HALF_STUDENT_T_LP: {
+            exf2 gd, gs;
+            ex2_student_t_grad(c0, x, z, gd, gs);
+            const exf2 a = -(c * gd), b = c * gs;
+            dx = exf2{x.x >= 0.0f ? a.x : 0.0f, x.y >= 0.0f ? a.y : 0.0f};
+            dz = exf2{x.x >= 0.0f ? b.x : 0.0f, x.y >= 0.0f ? b.y : 0.0f};
+            break;
+        }
         default: {
             float ax, ay, az, bx, by, bz;
             ex_bwd(op, x.x, y.x, z.x, v.x, c.x, c0, ax, ay, az);
@@ -1337,7 +1441,9 @@ MC_DEV void eval_expr_n(const DevTerm& T, const DevCtx& P, const float* q, float
     const bool split = seg && T.ncomb > 0;
     float val[NMAX], adj[NMAX], part[NMAX];
     // the node descriptors, read once per term: lane k of these registers
-    // holds node k (packed op / arguments / flags, leaf offsets, constant);
+    // holds node k (packed op / arguments / flags, leaf offsets, constant:
+    // the op in 6 bits, each argument + 1 in 5 — an argument precedes its node,
+    // so it is at most 30);
     // a node visit reads them with readlane into SGPRs (re-reading them from
     // constant memory per node and element cost ~20 scalar loads per element)
     int dcode = 0, dpoff = 0, dpool = 0;
@@ -1346,7 +1452,7 @@ MC_DEV void eval_expr_n(const DevTerm& T, const DevCtx& P, const float* q, float
         const int ln = G.tid & 63;
         if (ln < nn) {
             const MC_CONST DevExprNode* d = N + ln;
-            dcode = (d->op & 31) | ((d->a + 1) << 5) | ((d->b + 1) << 11) | ((d->c + 1) << 17) |
+            dcode = (d->op & 63) | ((d->a + 1) << 6) | ((d->b + 1) << 11) | ((d->c + 1) << 17) |
                     ((d->prim != 0 ? 1 : 0) << 23) | ((d->pass & 15) << 24) | ((d->leaf.kind & 7) << 28);
             dpoff = d->leaf.poff;
             dpool = (int)d->leaf.pool;
@@ -1354,8 +1460,8 @@ MC_DEV void eval_expr_n(const DevTerm& T, const DevCtx& P, const float* q, float
         }
     }
     auto code = [&](int k) { return __builtin_amdgcn_readlane(dcode, k); };
-    auto cop = [](int d) { return d & 31; };
-    auto carg = [](int d, int sh) { return ((d >> sh) & 63) - 1; };
+    auto cop = [](int d) { return d & 63; };
+    auto carg = [](int d, int sh) { return ((d >> sh) & 31) - 1; };
     auto cprim = [](int d) { return ((d >> 23) & 1) != 0; };
     auto cpass = [](int d) { return (d >> 24) & 15; };
     auto ckind = [](int d) { return (d >> 28) & 7; };
@@ -1388,7 +1494,7 @@ MC_DEV void eval_expr_n(const DevTerm& T, const DevCtx& P, const float* q, float
                         v = q[poff + P.index[__builtin_amdgcn_readlane(dpool, k) + e]];
                     }
                 } else {
-                    const int a = carg(d, 5), b = carg(d, 11), c = carg(d, 17);
+                    const int a = carg(d, 6), b = carg(d, 11), c = carg(d, 17);
                     v = ex_fwd(op, val[a], b >= 0 ? val[b] : 0.0f, c >= 0 ? val[c] : 0.0f,
                                cval_of(k));
                 }
@@ -1416,7 +1522,7 @@ MC_DEV void eval_expr_n(const DevTerm& T, const DevCtx& P, const float* q, float
                     }
                     continue;
                 }
-                const int a = carg(d, 5), b = carg(d, 11), c = carg(d, 17);
+                const int a = carg(d, 6), b = carg(d, 11), c = carg(d, 17);
                 float dx, dy, dz;
                 ex_bwd(op, val[a], b >= 0 ? val[b] : 0.0f, c >= 0 ? val[c] : 0.0f, val[k], ck,
                        cval_of(k), dx, dy, dz);

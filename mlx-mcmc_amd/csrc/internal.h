@@ -87,10 +87,16 @@ struct DevExprNode {
 // (recorded at program creation; predictive.h draws its replicates): kind an
 // mc_discrete_kind or -1 (no sampling distribution), node the count node, y /
 // tot / eta its argument nodes (tot -1 unless Binomial) — indices within the
-// term, all below `node`.
+// term, all below `node`.  The Student-t nodes (MC_EX_STUDENT_T_LP /
+// MC_EX_HALF_STUDENT_T_LP) are recorded by the same rule with the kinds below
+// (beyond mc_discrete_kind: not count terms, no ties): y the value, tot the loc
+// (-1 for the half form), eta the scale, nu the node's degrees of freedom.
+enum { PW_SAMPLER_STUDENT_T = 3, PW_SAMPLER_HALF_STUDENT_T = 4 };
 struct PwSampler {
     int32_t kind, node, y, tot, eta;
+    float nu;
 };
+constexpr PwSampler kPwNoSampler = {-1, -1, -1, -1, -1, 0.0f};
 
 struct DevCtx {
     const DevTerm* terms;

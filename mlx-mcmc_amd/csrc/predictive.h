@@ -90,6 +90,27 @@
 //     At most kPpAttempts attempts (PTRS and BTRS accept more than two in
 //     three), then NaN.
 //
+//   Student-t terms  an expression term whose root is MC_EX_STUDENT_T_LP /
+//             MC_EX_HALF_STUDENT_T_LP, or ADD(that node, a CONST / DATA leaf),
+//             is recorded and walked as the count terms are (PwSampler kinds
+//             PW_SAMPLER_STUDENT_T / PW_SAMPLER_HALF_STUDENT_T, nu in the
+//             descriptor); value, loc and scale are node values at the draw.
+//             pp_student_t, f32 IEEE operations and the samplers above only —
+//             the same function on host and device — one rule for every nu,
+//             Cauchy (nu = 1) included:
+//               NaN when !(s > 0), !(nu > 0) or m is NaN
+//               z0 = the first normal of mc_box_muller(w.x, w.y), attempt 0
+//               g  = pp_gamma_unit(nu / 2) on sub = 0x100 + attempt (Beta's
+//                    second-Gamma range; NaN when its attempts are exhausted)
+//               t  = z0 / sqrt(g / (nu / 2))
+//               Student-t: m + s t        half form: |s t|
+//             (a normal over the root of an independent chi-square over its
+//             degrees of freedom).  For nu < 2 the Gamma shape nu / 2 is below
+//             1, so the mc_expf_ref caveat above applies: host and device may
+//             differ in the last bit with philox.h's ~1e-8 probability, as for
+//             Gamma today.  These terms are not count terms: they run the
+//             NMAX kernel but add no ties (mc_program_num_count_terms).
+//
 //   k_predictive<GB>  grid (tiles, B) on the pointwise view (pointwise.h PwCtx,
 //                 tiles of <= 256 consecutive elements of one term), one
 //                 observation per thread, its operands decoded once into
@@ -372,6 +393,20 @@ MC_HD float pp_draw_discrete(int kind, float total, float eta, uint64_t seed, ui
     return pp_nan();
 }
 
+// The replicate of one observation of a Student-t term (header comment above):
+// m + s t or |s t| with t = z0 / sqrt(g / (nu / 2)), g ~ Gamma(nu / 2, 1).
+MC_HD float pp_student_t(float nu, float m, float s, bool half, uint64_t seed, uint32_t chain,
+                         uint32_t iter, uint32_t obs) {
+    if (!(s > 0.0f) || !(nu > 0.0f) || m != m) return pp_nan();
+    const mc_u32x4 w = mc_draw(seed, chain, iter, MC_RNG_TAG_PREDICT, 0u, obs);
+    float z0, z1;
+    mc_box_muller(w.x, w.y, &z0, &z1);
+    const float a = 0.5f * nu;
+    const float g = pp_gamma_unit(a, seed, chain, iter, 0x100u, obs);
+    const float t = z0 / sqrtf(g / a);
+    return half ? fabsf(s * t) : m + s * t;
+}
+
 #if defined(__HIPCC__)
 #include "pointwise.h"
 
@@ -414,7 +449,7 @@ __global__ __launch_bounds__(kPwBlock) void k_predictive(PwCtx P, PpRun R,
     }
 
     // a count term (wave-uniform, as the tile's term): its sampler
-    PwSampler sd = {-1, -1, -1, -1, -1};
+    PwSampler sd = kPwNoSampler;
     if constexpr (NMAX > 0) {
         if (T.dist == MC_DIST_EXPR) {
             const MC_CONST PwSampler* sp = cptr(samp) + __builtin_amdgcn_readfirstlane(tile.term);
@@ -423,6 +458,7 @@ __global__ __launch_bounds__(kPwBlock) void k_predictive(PwCtx P, PpRun R,
             sd.y = sp->y;
             sd.tot = sp->tot;
             sd.eta = sp->eta;
+            sd.nu = sp->nu;
         }
     }
 
@@ -448,9 +484,16 @@ __global__ __launch_bounds__(kPwBlock) void k_predictive(PwCtx P, PpRun R,
                     float val[NMAX];
                     pw_expr_walk<NMAX>(T, P, q, i, sd.node, val);
                     v = val[sd.y];
-                    y = pp_draw_discrete(sd.kind, sd.tot >= 0 ? val[sd.tot] : 0.0f, val[sd.eta],
-                                         R.seed, R.chain0 + (uint32_t)c, R.iter0 + (uint32_t)s,
+                    const float tot = sd.tot >= 0 ? val[sd.tot] : 0.0f;
+                    if (sd.kind >= PW_SAMPLER_STUDENT_T)
+                        y = pp_student_t(sd.nu, tot, val[sd.eta],
+                                         sd.kind == PW_SAMPLER_HALF_STUDENT_T, R.seed,
+                                         R.chain0 + (uint32_t)c, R.iter0 + (uint32_t)s,
                                          (uint32_t)o);
+                    else
+                        y = pp_draw_discrete(sd.kind, tot, val[sd.eta], R.seed,
+                                             R.chain0 + (uint32_t)c, R.iter0 + (uint32_t)s,
+                                             (uint32_t)o);
                 }
             } else {
                 v = pw_value(ov, q);

@@ -551,7 +551,8 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
         d.c = s.c;
         d.leaf.kind = MC_OP_NONE;
         d.leaf.slot = -1;
-        if (s.op < MC_EX_LEAF || s.op > MC_EX_PICK || s.op == 28)  // (28: not assigned)
+        if (s.op < MC_EX_LEAF || s.op > MC_EX_HALF_STUDENT_T_LP || s.op == 28 ||
+            s.op == 31)  // (28, 31: not assigned)
             return fail(MC_ERR_INVALID, "term %d node %d: unknown op %d", t, k, s.op);
         if (s.op == MC_EX_LEAF) {
             const mc_operand& o = s.leaf;
@@ -611,10 +612,10 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
                 ub = true;
                 break;
             case MC_EX_NORMAL_LP: case MC_EX_WHERE: case MC_EX_GAMMA_LP: case MC_EX_BETA_LP:
-            case MC_EX_BINOMIAL_LOGIT_LP: case MC_EX_PICK:
+            case MC_EX_BINOMIAL_LOGIT_LP: case MC_EX_PICK: case MC_EX_STUDENT_T_LP:
                 ub = uc = true;
                 break;
-            case MC_EX_HALFNORMAL_LP: case MC_EX_EXPONENTIAL_LP:
+            case MC_EX_HALFNORMAL_LP: case MC_EX_EXPONENTIAL_LP: case MC_EX_HALF_STUDENT_T_LP:
                 uc = true;
                 break;
             default:
@@ -653,6 +654,14 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
                 return fail(MC_ERR_UNSUPPORTED, "term %d node %d: the pick node's label y must be "
                             "data or a constant", t, k);
             d.leaf.cval = s.leaf.value;
+        }
+        // the Student-t nodes: nu is the node's own constant, finite and positive
+        if (s.op == MC_EX_STUDENT_T_LP || s.op == MC_EX_HALF_STUDENT_T_LP) {
+            const float nu = s.leaf.value;
+            if (!(nu > 0.0f) || !(nu < __builtin_inff()))
+                return fail(MC_ERR_INVALID, "term %d node %d: the Student-t node's degrees of "
+                            "freedom must be finite and positive (got %g)", t, k, (double)nu);
+            d.leaf.cval = nu;
         }
         // the distribution nodes' f32 normalisers (elem_normal / elem_halfnormal)
         if (s.op == MC_EX_NORMAL_LP) d.leaf.cval = dist_c0(MC_DIST_NORMAL);
@@ -779,9 +788,13 @@ static int build_expr_term(int32_t t, const mc_term& src, const mc_expr* exprs, 
 // The sampler descriptor of an expression term (internal.h PwSampler) from its
 // validated nodes.
 static PwSampler expr_sampler(const DevExprNode* N, int nn) {
-    PwSampler sd = {-1, -1, -1, -1, -1};
-    auto count_node = [](int op) {
-        return op >= MC_EX_BERNOULLI_LOGIT_LP && op <= MC_EX_POISSON_LOG_LP;
+    PwSampler sd = kPwNoSampler;
+    auto student_node = [](int op) {
+        return op == MC_EX_STUDENT_T_LP || op == MC_EX_HALF_STUDENT_T_LP;
+    };
+    auto count_node = [&](int op) {  // (a node with a sampler: count or Student-t)
+        return (op >= MC_EX_BERNOULLI_LOGIT_LP && op <= MC_EX_POISSON_LOG_LP) ||
+               student_node(op);
     };
     auto fixed_leaf = [&](int k) {
         return N[k].op == MC_EX_LEAF &&
@@ -794,6 +807,15 @@ static PwSampler expr_sampler(const DevExprNode* N, int nn) {
     else if (r.op == MC_EX_ADD && count_node(N[r.b].op) && fixed_leaf(r.a)) node = r.b;
     if (node < 0) return sd;
     const DevExprNode& d = N[node];
+    if (student_node(d.op)) {  // y the value, tot the loc (-1: half form), eta the scale
+        sd.kind = d.op == MC_EX_STUDENT_T_LP ? PW_SAMPLER_STUDENT_T : PW_SAMPLER_HALF_STUDENT_T;
+        sd.node = node;
+        sd.y = d.a;
+        sd.tot = d.b;
+        sd.eta = d.c;
+        sd.nu = d.leaf.cval;
+        return sd;
+    }
     sd.kind = d.op - MC_EX_BERNOULLI_LOGIT_LP;  // mc_discrete_kind, in op order
     sd.node = node;
     sd.y = d.a;
@@ -1006,7 +1028,7 @@ extern "C" int mc_program_create_expr(const mc_term* terms, int32_t n_terms,
         pwt.clogs = dt.clogs;
         pwt.clg = dt.clg;
         pws.push_back(pwt);
-        pwsd.push_back(PwSampler{-1, -1, -1, -1, -1});
+        pwsd.push_back(kPwNoSampler);
         // pass planning: accumulating vector operands with overlapping parameter
         // ranges go to different sweeps
         int64_t lo[3], hi[3];

@@ -1,6 +1,7 @@
 // run_predictive.hip — posterior predictive replicates on the pointwise view
 // of a program (csrc/predictive.h): mc_predictive_draw and
-// mc_predictive_draw_discrete (the scalar definitions, host only),
+// mc_predictive_draw_discrete / mc_predictive_draw_student_t (the scalar
+// definitions, host only),
 // mc_predictive_workspace_bytes, mc_predictive, mc_predictive_eq.
 #include "host.h"
 #include "predictive.h"
@@ -16,7 +17,8 @@ struct PpPlan {
     const PwView* v;
     int64_t Sp, Np, B, per;
     bool gb;
-    int nmax;  // 0: no count term; 16 / 32: the largest one's node bound
+    int nmax;  // 0: no expression sampler; 16 / 32: the largest one's node bound
+    bool ties;  // a count term: EQUAL is counted (a sixth f64 per block and observation)
 };
 int pp_plan(const mc_program* p, int64_t C, int64_t S, int64_t thin, PpPlan* out) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
@@ -27,11 +29,14 @@ int pp_plan(const mc_program* p, int64_t C, int64_t S, int64_t thin, PpPlan* out
     if (C > INT64_MAX / S) return fail(MC_ERR_INVALID, "predictive: C * S overflows");
     bool gb = false;
     int nmax = 0;
+    bool ties = false;
     for (size_t t = 0; t < p->pw_terms.size(); ++t) {
         const int dist = p->pw_terms[t].dist;
-        // an expression term whose root is a count node (internal.h PwSampler)
+        // an expression term whose root is a count or Student-t node (internal.h
+        // PwSampler)
         if (dist == MC_DIST_EXPR && t < p->pw_samplers.size() && p->pw_samplers[t].kind >= 0) {
             nmax = std::max(nmax, p->pw_terms[t].expr_n > 16 ? 32 : 16);
+            ties |= p->pw_samplers[t].kind < PW_SAMPLER_STUDENT_T;
             continue;
         }
         if (!pp_sampled(dist))
@@ -48,12 +53,13 @@ int pp_plan(const mc_program* p, int64_t C, int64_t S, int64_t thin, PpPlan* out
     out->Np = C * out->Sp;
     out->gb = gb;
     out->nmax = nmax;
+    out->ties = ties;
     pw_split(out->Np, v->ntiles, &out->B, &out->per);
     return MC_OK;
 }
 int64_t pp_need(const PpPlan& L) {
     // (the five fields per block; with count terms the ties' count as well)
-    return L.B > 1 ? L.B * (PP_COUNT + (L.nmax > 0 ? 1 : 0)) * L.v->M * (int64_t)sizeof(double)
+    return L.B > 1 ? L.B * (PP_COUNT + (L.ties ? 1 : 0)) * L.v->M * (int64_t)sizeof(double)
                    : 0;
 }
 
@@ -80,10 +86,19 @@ extern "C" int mc_predictive_draw_discrete(int kind, float total, float eta, uin
     return MC_OK;
 }
 
+extern "C" int mc_predictive_draw_student_t(float df, float loc, float scale, int half,
+                                            uint64_t seed, uint32_t chain, uint32_t iter,
+                                            uint32_t obs, float* out) {
+    if (!out) return fail(MC_ERR_INVALID, "predictive: out is NULL");
+    *out = pp_student_t(df, loc, scale, half != 0, seed, chain, iter, obs);
+    return MC_OK;
+}
+
 extern "C" int32_t mc_program_num_count_terms(const mc_program* p) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
     int32_t n = 0;
-    for (const PwSampler& sd : p->pw_samplers) n += sd.kind >= 0 ? 1 : 0;
+    for (const PwSampler& sd : p->pw_samplers)
+        n += sd.kind >= 0 && sd.kind < PW_SAMPLER_STUDENT_T ? 1 : 0;
     return n;
 }
 
@@ -110,7 +125,7 @@ extern "C" int mc_predictive_eq(const mc_program* p, int64_t C, int64_t S, int64
     const int rc = pp_plan(p, C, S, thin, &L);
     if (rc != MC_OK) return rc;
     if (!samples || !stats) return fail(MC_ERR_INVALID, "predictive: NULL samples / stats");
-    if (equal && L.nmax == 0)
+    if (equal && !L.ties)
         return fail(MC_ERR_UNSUPPORTED, "predictive: the count of ties needs a likelihood with "
                     "a count term (pass equal = NULL)");
     if (chain_offset < 0 || chain_offset + C > (int64_t)UINT32_MAX)
@@ -141,8 +156,8 @@ extern "C" int mc_predictive_eq(const mc_program* p, int64_t C, int64_t S, int64
         hipLaunchKernelGGL(kernel, grid, dim3(kPwBlock), 0, st, X, R, samples, part, yrep,
                            (const PwSampler*)L.v->d_samplers, eqpart);
     };
-    // programs with count terms run the NMAX > 0 kernel (it carries every
-    // sampler); everything else the kernels without that path
+    // programs with count or Student-t terms run the NMAX > 0 kernel (it
+    // carries every sampler); everything else the kernels without that path
     const int nmax = L.nmax;
     if (nmax > 16) launch(k_predictive<true, 32>);
     else if (nmax > 0) launch(k_predictive<true, 16>);

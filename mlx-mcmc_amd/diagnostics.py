@@ -659,7 +659,8 @@ def posterior_predictive(log_likelihood_fn, samples, layout=None, *, seed=0, thi
     observation, one replicate is drawn from the term's distribution — Normal,
     HalfNormal, Exponential, Gamma or Beta, or the count distribution of a
     ``Bernoulli(logits=)`` / ``Binomial(n, logits=)`` / ``Poisson(log_rate=)``
-    likelihood term — with the operand values of that draw.  A replicate is a pure function of (``seed``, chain index +
+    likelihood term, or the ``StudentT`` / ``Cauchy`` / ``HalfStudentT`` /
+    ``HalfCauchy`` of such a term — with the operand values of that draw.  A replicate is a pure function of (``seed``, chain index +
     ``chain_offset``, iteration index + ``iter_offset``, observation) and those
     operand values (include/mcmc355.h), so shards of chains or iterations and
     thinned runs reproduce the rows of the whole.  A term's weight (``mx.mean``,

@@ -1,6 +1,7 @@
 """Distributions of the tape: ``Distribution``, ``Normal``, ``HalfNormal``,
 ``Exponential``, ``Gamma``, ``Beta``, the count likelihoods ``Bernoulli``,
-``Binomial``, ``Poisson``, and ``Categorical``.
+``Binomial``, ``Poisson``, ``Categorical``, and the Student-t family ``StudentT``,
+``Cauchy``, ``HalfStudentT``, ``HalfCauchy``.
 
 Same constructor arguments, ``log_prob(value)`` / ``sample(key, shape)``
 contract and formulas as the reference (mlx_mcmc/distributions/base.py:6-54,
@@ -34,6 +35,18 @@ log mass of a label y in 0 .. K-1 under K class arguments:
   log p(y) = eta_y - log sum_k exp(eta_k),  eta_k the logits or log(p_k)
   (-inf for a label outside 0 .. K-1; traced, two chained expression nodes —
   a selection by the label and a pairwise log-sum-exp; see the class)
+
+``StudentT(df, loc, scale)``, ``Cauchy(loc, scale)``, ``HalfStudentT(df, scale)``
+and ``HalfCauchy(scale)`` (not in the reference; the Cauchy classes are df = 1)
+are heavy-tailed likelihoods and weakly informative scale priors with a
+constant df:
+
+  StudentT:     log p(x) = C(df) - log(scale) - (df + 1) / 2 log1p(z^2 / df),
+                z = (x - loc) / scale,
+                C(df) = lgamma((df + 1) / 2) - lgamma(df / 2) - log(df pi) / 2
+  HalfStudentT: log 2 + the same with loc = 0 for x >= 0, -inf otherwise
+  (one expression node plus the normaliser constant; concrete values go
+  through ``mc_student_t_log_prob``; ``sample`` draws on the host)
 
 Inside a traced ``log_prob(params)`` (any argument is a traced parameter),
 ``log_prob`` records a fused term for the HIP tape (see _trace.py).  On
@@ -564,5 +577,148 @@ class Categorical(Distribution):
         return f"Categorical(num_categories={self.num_categories})"
 
 
+def _gpu_student_t_log_prob(df: float, half: bool, value, loc, scale) -> np.ndarray:
+    """The Student-t node's value on concrete arguments (mc_student_t_log_prob)
+    plus the f32 normaliser, added in f32 as the traced ADD node adds it."""
+    import torch
+
+    dev = _lib.require_device()
+    v, s = _to_f32(value), _to_f32(scale)
+    m = None if half else _to_f32(loc)
+    shapes = [a.shape for a in (v, m, s) if a is not None]
+    out_shape = np.broadcast_shapes(*shapes)
+    n = int(np.prod(out_shape)) if out_shape else 1
+
+    def dev_arr(a):
+        if a is None:
+            return None, 1
+        if a.size == 1:
+            return torch.from_numpy(a.reshape(1).copy()).to(dev), 1
+        return torch.from_numpy(np.broadcast_to(a, out_shape).reshape(-1).copy()).to(dev), 0
+
+    tv, bv = dev_arr(v)
+    tm, bm = dev_arr(m)
+    ts, bs = dev_arr(s)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().mc_student_t_log_prob(df, int(half), n, _lib.ptr(tv), bv, _lib.ptr(tm),
+                                                 bm, _lib.ptr(ts), bs, _lib.ptr(out),
+                                                 _lib.stream_handle()))
+    core = out.cpu().numpy().reshape(out_shape)
+    with np.errstate(invalid="ignore"):
+        return (core + _trace.student_t_norm(df, half)).astype(np.float32)
+
+
+class StudentT(Distribution):
+    """StudentT(df, loc=0.0, scale=1.0): the location-scale Student-t,
+
+      log p(x) = lgamma((df + 1) / 2) - lgamma(df / 2) - log(df pi) / 2 - log(scale)
+                 - (df + 1) / 2 * log1p(((x - loc) / scale)^2 / df)
+
+    df is a constant — one finite positive number (ValueError otherwise; a
+    traced df is a TraceError: its normaliser would need an lgamma node with a
+    digamma VJP); value, loc and scale may each be traced, data or constants.
+    Traced, ``log_prob`` records ADD(MC_EX_STUDENT_T_LP, normaliser): three
+    nodes beside its arguments (_trace.student_t_expr)."""
+
+    _half = False
+
+    def __init__(self, df, loc=0.0, scale=1.0):
+        self.df = _trace.student_t_df(type(self).__name__, df)
+        self.loc = loc
+        self.scale = scale
+
+    def log_prob(self, value):
+        name = type(self).__name__
+        if _trace.is_symbolic(value, self.loc, self.scale):
+            return _trace.student_t_expr(name, self.df, value, self.loc, self.scale, self._half)
+        return _gpu_student_t_log_prob(self.df, self._half, value, self.loc, self.scale)
+
+    def _standard(self, key, shape):
+        """Standard t draws on the host (NumPy seeded from the key, as Gamma's)."""
+        return _host_rng(key).standard_t(self.df, size=shape or None)
+
+    def sample(self, key, shape=()):
+        t = self._standard(key, shape)
+        return (_to_f32(self.loc) + _to_f32(self.scale) * t).astype(np.float32)
+
+    def mean(self):
+        loc = _to_f32(self.loc)
+        return loc if self.df > 1.0 else np.full_like(loc, np.nan)
+
+    def variance(self):
+        s2 = _to_f32(self.scale) ** 2
+        if self.df > 2.0:
+            return (s2 * np.float32(self.df / (self.df - 2.0))).astype(np.float32)
+        return np.full_like(s2, np.inf if self.df > 1.0 else np.nan)
+
+    def mode(self):
+        return _to_f32(self.loc)
+
+    def __repr__(self):
+        return (f"StudentT(df={self.df:.3f}, loc={_scalar_repr(self.loc)}, "
+                f"scale={_scalar_repr(self.scale)})")
+
+
+class Cauchy(StudentT):
+    """Cauchy(loc=0.0, scale=1.0): StudentT with df = 1."""
+
+    def __init__(self, loc=0.0, scale=1.0):
+        super().__init__(1.0, loc, scale)
+
+    def __repr__(self):
+        return f"Cauchy(loc={_scalar_repr(self.loc)}, scale={_scalar_repr(self.scale)})"
+
+
+class HalfStudentT(StudentT):
+    """HalfStudentT(df, scale=1.0): |T| for T ~ StudentT(df, 0, scale) — twice
+    its density on x >= 0, -inf below (MC_EX_HALF_STUDENT_T_LP; HalfNormal's
+    convention at the edge)."""
+
+    _half = True
+
+    def __init__(self, df, scale=1.0):
+        super().__init__(df, 0.0, scale)
+
+    def sample(self, key, shape=()):
+        return np.abs(_to_f32(self.scale) * self._standard(key, shape)).astype(np.float32)
+
+    def mean(self):
+        # E|T| = 2 sqrt(df) Gamma((df + 1) / 2) / ((df - 1) sqrt(pi) Gamma(df / 2))
+        import math
+
+        s = _to_f32(self.scale)
+        if not self.df > 1.0:
+            return np.full_like(s, np.inf)
+        nu = self.df
+        c = (2.0 * math.sqrt(nu) / ((nu - 1.0) * math.sqrt(math.pi))
+             * math.exp(math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu)))
+        return (s * np.float32(c)).astype(np.float32)
+
+    def variance(self):
+        s2 = _to_f32(self.scale) ** 2
+        if not self.df > 2.0:
+            return np.full_like(s2, np.inf if self.df > 1.0 else np.nan)
+        nu = self.df
+        m = self.mean().astype(np.float64)
+        return (s2 * (nu / (nu - 2.0)) - m * m).astype(np.float32)
+
+    def mode(self):
+        return np.zeros_like(_to_f32(self.scale))
+
+    def __repr__(self):
+        return f"HalfStudentT(df={self.df:.3f}, scale={_scalar_repr(self.scale)})"
+
+
+class HalfCauchy(HalfStudentT):
+    """HalfCauchy(scale=1.0): HalfStudentT with df = 1."""
+
+    def __init__(self, scale=1.0):
+        super().__init__(1.0, scale)
+
+    def __repr__(self):
+        return f"HalfCauchy(scale={_scalar_repr(self.scale)})"
+
+
 __all__ = ["Distribution", "Normal", "HalfNormal", "Exponential", "Gamma", "Beta", "Bernoulli",
-           "Binomial", "Poisson", "Categorical", "Key"]
+           "Binomial", "Poisson", "Categorical", "StudentT", "Cauchy", "HalfStudentT",
+           "HalfCauchy", "Key"]
