@@ -1142,6 +1142,64 @@ int mc_rank_diag(int64_t C, int64_t S, int64_t D, const float* samples_dev, doub
 int mc_geyer_ess_host(const double* rho, int64_t n, int64_t N, double* ess);
 int mc_debug_rank_path(int path);
 
+/* ---- design-matrix GLMs (no reference code: its models are written term by
+ * term) --------------------------------------------------------------------
+ * A log density  sum_i family(y_i | eta_i) + priors  with the linear predictor
+ *     eta = X beta  [+ intercept]  [+ offset]
+ * over a dense row-major design matrix X[N, P] in the float data pool.  C
+ * chains are batched as the N dimension of two FP32 MFMA products per
+ * gradient, eta[N, C] = X B and G[P, C] = X^T R (csrc/glm.h): X is read once
+ * per block of 32 chains instead of once per chain.
+ *   family     MC_GLM_NORMAL: Normal(eta, scale).log_prob(y) (MC_EX_NORMAL_LP's
+ *              device function); MC_GLM_BERNOULLI_LOGIT / MC_GLM_POISSON_LOG:
+ *              the count nodes' functions, without the normaliser (a constant
+ *              of the data: the caller adds its sum to lp_const)
+ *   beta       the P parameters q[beta_offset .. beta_offset + P)
+ *   intercept  MC_OP_NONE, MC_OP_CONST or MC_OP_PSCALAR (no transform)
+ *   offset     offset_pool < 0: none, else N floats of the data pool
+ *   scale      normal family: MC_OP_CONST or MC_OP_PSCALAR, transform
+ *              MC_XF_NONE or MC_XF_EXP; ignored by the other families
+ * The prior terms are fused terms whose value is a parameter operand
+ * (PSCALAR / PVEC, any transform) or MC_DIST_IDENTITY terms, with CONST (or
+ * unused) loc and scale; anything else is MC_ERR_UNSUPPORTED.
+ * Limits, each MC_ERR_UNSUPPORTED before any device work: 1 <= P <=
+ * MC_GLM_MAX_P (the gradient block of 32 chains lives in accumulator
+ * registers, 16 per 32 coefficients), N >= 1, the padded N * P below 2^31.
+ * The result is an ordinary mc_program for mc_state_bytes / _offsets / _init,
+ * mc_logp_grad, mc_hmc_run / mc_hmc_workspace_bytes, mc_program_set_slices /
+ * _num_slices / _kernel_note / _num_params / _destroy (mc_program_slice_kernel
+ * returns 3); every other entry point that takes a program returns
+ * MC_ERR_UNSUPPORTED (or -1 / 0 where it returns a count).  num_slices here
+ * is row slices per chain block: 0 automatic (enough that slices x chain
+ * blocks cover the CUs, at most 64 and at most one 32-row tile per wave),
+ * 1..64 that many.  A chain's draws are those of mc_hmc_run on the tape up to
+ * fp32 summation order, and are the same bits however the chains are split
+ * over launches, chain blocks and GPUs at a fixed slice count.  mc_logp_grad
+ * and mc_state_init stage their partial sums in a buffer the program owns:
+ * calls on one program must be ordered on one stream.                       */
+#define MC_GLM_NORMAL          0
+#define MC_GLM_BERNOULLI_LOGIT 1
+#define MC_GLM_POISSON_LOG     2
+#define MC_GLM_MAX_P           256
+typedef struct mc_glm {
+    int32_t    family;        /* MC_GLM_*                                    */
+    int32_t    beta_offset;   /* parameter offset of beta[0]                 */
+    int64_t    n, p;          /* rows and columns of X                       */
+    int64_t    x_pool;        /* data pool offset of X (row-major, n * p)    */
+    int64_t    y_pool;        /* data pool offset of y (n)                   */
+    int64_t    offset_pool;   /* data pool offset of the offset (n), or -1   */
+    mc_operand intercept;
+    mc_operand scale;
+} mc_glm;
+int mc_program_create_glm(const mc_glm* glm, const mc_term* priors, int32_t n_priors,
+                          int32_t n_params, float lp_const,
+                          const float* data, int64_t n_data, mc_program** out);
+/* The plan of a design-matrix program (0 for any other program, -1 on NULL):
+ * the row slices a launch of num_chains chains uses, and the chains per block
+ * (the MFMA tile's N dimension, 32).                                        */
+int32_t mc_program_glm_slices(const mc_program* prog, int64_t num_chains);
+int32_t mc_program_glm_chain_block(const mc_program* prog);
+
 const char* mc_last_error(void);
 int32_t mc_abi_version(void);
 

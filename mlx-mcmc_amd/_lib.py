@@ -147,6 +147,26 @@ class McExpr(ctypes.Structure):
     ]
 
 
+# mc_glm families (design-matrix programs, mc_program_create_glm)
+MC_GLM_NORMAL, MC_GLM_BERNOULLI_LOGIT, MC_GLM_POISSON_LOG = range(3)
+MC_GLM_MAX_P = 256
+
+
+class McGlm(ctypes.Structure):
+    """mc_glm: eta = X beta [+ intercept] [+ offset] under one of the families."""
+    _fields_ = [
+        ("family", ctypes.c_int32),
+        ("beta_offset", ctypes.c_int32),
+        ("n", ctypes.c_int64),
+        ("p", ctypes.c_int64),
+        ("x_pool", ctypes.c_int64),
+        ("y_pool", ctypes.c_int64),
+        ("offset_pool", ctypes.c_int64),
+        ("intercept", McOperand),
+        ("scale", McOperand),
+    ]
+
+
 class McChainScalars(ctypes.Structure):
     _fields_ = [
         ("step_size", ctypes.c_double),
@@ -223,6 +243,11 @@ SIGNATURES = [
       ctypes.POINTER(McExpr), ctypes.c_int32, ctypes.POINTER(McExprNode), ctypes.c_int32,
       ctypes.c_int32, ctypes.c_float, _VP, ctypes.c_int64, _VP, ctypes.c_int64,
       ctypes.POINTER(_VP)]),
+    ("mc_program_create_glm", ctypes.c_int,
+     [ctypes.POINTER(McGlm), ctypes.POINTER(McTerm), ctypes.c_int32, ctypes.c_int32,
+      ctypes.c_float, _VP, ctypes.c_int64, ctypes.POINTER(_VP)]),
+    ("mc_program_glm_slices", ctypes.c_int32, [_VP, ctypes.c_int64]),
+    ("mc_program_glm_chain_block", ctypes.c_int32, [_VP]),
     ("mc_program_destroy", ctypes.c_int, [_VP]),
     ("mc_program_num_params", ctypes.c_int32, [_VP]),
     ("mc_program_waves_per_chain", ctypes.c_int32, [_VP]),

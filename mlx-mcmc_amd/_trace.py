@@ -207,6 +207,13 @@ class Param:
 
     # affine arithmetic (a + b * x, the fast fused paths): see Affine; any
     # other elementwise arithmetic builds an expression (Expr)
+    # X @ beta: a design-matrix linear predictor (MatVec)
+    def __rmatmul__(self, other):
+        return MatVec.of(other, self)
+
+    def __matmul__(self, other):
+        raise TraceError("beta @ X: the matrix is the left operand; " + _GLM_FORM)
+
     def __mul__(self, other):
         if isinstance(other, LogProbExpr):  # theta * lp: a traced weight
             return other * self
@@ -222,14 +229,14 @@ class Param:
         return _affine_or_expr(lambda: Affine.product(other, self), _lib.MC_EX_MUL, other, self)
 
     def __add__(self, other):
-        if isinstance(other, LogProbExpr):
+        if isinstance(other, (LogProbExpr, MatVec)):
             return other + self
         if isinstance(other, Expr):
             return Expr.binary(_lib.MC_EX_ADD, self, other)
         return _affine_or_expr(lambda: Affine.lift(self) + other, _lib.MC_EX_ADD, self, other)
 
     def __radd__(self, other):
-        if isinstance(other, LogProbExpr):
+        if isinstance(other, (LogProbExpr, MatVec)):
             return other + self
         if isinstance(other, Expr):
             return Expr.binary(_lib.MC_EX_ADD, other, self)
@@ -277,6 +284,136 @@ class Param:
     def __repr__(self):
         xf = {1: "exp ", 2: "log "}.get(self.xf, "")
         return f"Param({xf}{self.name}, view={self.view})"
+
+
+_GLM_FORM = (
+    "a design-matrix model is eta = X @ beta (X a 2-D float data array [N, P], beta a whole "
+    "vector parameter or a contiguous slice of one, of length P), plus at most a constant, a "
+    "scalar parameter (the intercept) and a data vector (an offset), used as exactly one of "
+    "Normal(eta, s).log_prob(y) with s a constant, a scalar parameter or mx.exp of one, "
+    "Bernoulli(logits=eta).log_prob(y) or Poisson(log_rate=eta).log_prob(y), y data of length "
+    "N, summed whole with mx.sum, beside Normal / HalfNormal / Exponential / Gamma / Beta "
+    "priors with constant arguments on the parameters")
+
+GLM_DIST = 100  # Term.dist of the design-matrix likelihood (Python side only)
+GLM_FAMILIES = {"Normal": _lib.MC_GLM_NORMAL, "Bernoulli": _lib.MC_GLM_BERNOULLI_LOGIT,
+                "Poisson": _lib.MC_GLM_POISSON_LOG}
+
+
+class MatVec:
+    """A traced linear predictor X @ beta [+ constant] [+ intercept] [+ offset]
+    (include/mcmc355.h mc_glm): only sums extend it, and only the three GLM
+    likelihoods consume it."""
+
+    __array_priority__ = 1000
+
+    def __init__(self, X, beta, const=0.0, icpt=None, offset=None):
+        self.X = X            # float32 [N, P]
+        self.beta = beta      # (parameter offset of beta[0], P)
+        self.const = const
+        self.icpt = icpt      # a scalar Param, or None
+        self.offset = offset  # float32 [N], or None
+        self.shape = (X.shape[0],)
+
+    @staticmethod
+    def of(X, beta) -> "MatVec":
+        if not isinstance(beta, Param) or is_symbolic(X):
+            raise TraceError("a matrix product of two traced values: " + _GLM_FORM)
+        arr = np.asarray(_to_numpy(X))
+        if arr.dtype == object or arr.dtype.kind not in "fiu" or arr.ndim != 2:
+            raise TraceError(f"X @ beta with X of shape {arr.shape}: " + _GLM_FORM)
+        if beta.xf or len(beta.base_shape) != 1 or (beta.view is not None
+                                                    and beta.view[0] != "slice"):
+            raise TraceError(f"X @ beta with beta = {beta!r} (a multi-dimensional, gathered, "
+                             "scalar or transformed parameter): " + _GLM_FORM)
+        start = beta.view[1] if beta.view is not None else 0
+        if beta.size != arr.shape[1]:
+            raise TraceError(f"X @ beta: X has {arr.shape[1]} columns, beta {beta.size} "
+                             "elements")
+        return MatVec(np.ascontiguousarray(arr, np.float32), (beta.offset + start, beta.size))
+
+    def __add__(self, other):
+        if isinstance(other, MatVec):
+            raise TraceError("two matvec terms (X1 @ b1 + X2 @ b2: stack the columns into one "
+                             "design matrix): " + _GLM_FORM)
+        if isinstance(other, Param):
+            if other.shape != () or other.xf or self.icpt is not None:
+                raise TraceError("X @ beta plus a parameter that is not one untransformed "
+                                 "scalar intercept: " + _GLM_FORM)
+            return MatVec(self.X, self.beta, self.const, other, self.offset)
+        if isinstance(other, Expr) and other.op == _lib.MC_EX_ADD and all(
+                a.op == _lib.MC_EX_LEAF and (isinstance(a.leaf, (float, Param)))
+                for a in other.args):
+            # (c + a) + X @ beta: a constant and the intercept, added first
+            return (self + other.args[0].leaf) + other.args[1].leaf
+        if is_symbolic(other):
+            raise TraceError("a matvec inside another expression: " + _GLM_FORM)
+        arr = np.asarray(_to_numpy(other))
+        if arr.dtype == object or arr.shape not in ((), self.shape):
+            raise TraceError(f"X @ beta plus a value of shape {arr.shape}: " + _GLM_FORM)
+        arr = arr.astype(np.float32)
+        if arr.ndim == 0:
+            return MatVec(self.X, self.beta, float(np.float32(self.const) + arr), self.icpt,
+                          self.offset)
+        off = arr if self.offset is None else (self.offset + arr).astype(np.float32)
+        return MatVec(self.X, self.beta, self.const, self.icpt, off)
+
+    __radd__ = __add__
+
+    def _inside(self, *a, **k):
+        raise TraceError("a matvec inside another expression (only + of a constant, a scalar "
+                         "parameter or a data vector extends X @ beta): " + _GLM_FORM)
+
+    __sub__ = __rsub__ = __mul__ = __rmul__ = __truediv__ = __rtruediv__ = _inside
+    __pow__ = __rpow__ = __neg__ = __abs__ = __getitem__ = __matmul__ = __rmatmul__ = _inside
+    __lt__ = __le__ = __gt__ = __ge__ = __float__ = __bool__ = _inside
+
+    def __repr__(self):
+        return f"MatVec(X{list(self.X.shape)} @ params[{self.beta[0]}:+{self.beta[1]}])"
+
+
+@dataclass
+class GlmSpec:
+    """The design-matrix likelihood of a traced model (mc_glm)."""
+    family: int
+    eta: MatVec
+    y: np.ndarray
+    scale: Optional["Operand"] = None  # the normal family's scale
+    lp_const: float = 0.0              # the count normaliser's sum (Poisson)
+
+    @property
+    def N(self) -> int:
+        return int(self.eta.X.shape[0])
+
+    @property
+    def P(self) -> int:
+        return int(self.eta.X.shape[1])
+
+
+def glm_term(name: str, eta: MatVec, value, scale=None) -> "LogProbExpr":
+    """Normal(eta, s) / Bernoulli(logits=eta) / Poisson(log_rate=eta).log_prob(y)
+    over a traced X @ beta: one term, summed whole by mx.sum."""
+    if is_symbolic(value):
+        raise TraceError(f"{name}(X @ beta ...).log_prob of a traced value: " + _GLM_FORM)
+    y = np.asarray(_to_numpy(value))
+    if y.dtype == object or y.shape != eta.shape:
+        raise TraceError(f"{name}(X @ beta ...).log_prob(y) with y of shape {y.shape}, X of "
+                         f"{eta.shape[0]} rows: " + _GLM_FORM)
+    y = np.ascontiguousarray(y, np.float32)
+    spec = GlmSpec(GLM_FAMILIES[name], eta, y)
+    if name == "Normal":
+        if isinstance(scale, (MatVec, Affine, Expr, LogProbExpr)):
+            raise TraceError("Normal(X @ beta, s) with a traced expression as s: " + _GLM_FORM)
+        op = to_operand(scale)
+        if not (op.kind == _lib.MC_OP_CONST or (op.kind == _lib.MC_OP_PSCALAR and op.transform
+                                                in (_lib.MC_XF_NONE, _lib.MC_XF_EXP))):
+            raise TraceError("Normal(X @ beta, s) with s neither a constant, a scalar parameter "
+                             "nor mx.exp of one: " + _GLM_FORM)
+        spec.scale = op
+    elif name == "Poisson":
+        spec.lp_const = float(np.sum(discrete_norm("Poisson", y), dtype=np.float64))
+    term = Term(GLM_DIST, NONE_OPERAND, NONE_OPERAND, NONE_OPERAND, spec.N, glm=spec)
+    return LogProbExpr([term], 0.0, eta.shape)
 
 
 def _is_slope(x) -> bool:
@@ -481,6 +618,8 @@ class Expr:
     def of(x) -> "Expr":
         if isinstance(x, Expr):
             return x
+        if isinstance(x, MatVec):
+            raise TraceError("a matvec inside another expression: " + _GLM_FORM)
         if isinstance(x, LogProbExpr):
             raise TraceError("a log density inside a parameter expression or as a distribution "
                              "argument (only + / - / scalar * / mx.sum / mx.mean combine log "
@@ -537,12 +676,12 @@ class Expr:
 
     # -- arithmetic ------------------------------------------------------------
     def __add__(self, other):
-        if isinstance(other, LogProbExpr):
+        if isinstance(other, (LogProbExpr, MatVec)):
             return other + self
         return Expr.binary(_lib.MC_EX_ADD, self, other)
 
     def __radd__(self, other):
-        if isinstance(other, LogProbExpr):
+        if isinstance(other, (LogProbExpr, MatVec)):
             return other + self
         return Expr.binary(_lib.MC_EX_ADD, other, self)
 
@@ -727,6 +866,13 @@ def discrete_expr(name: str, value, total, arg, natural: bool) -> "LogProbExpr":
     is the logit / log rate; otherwise it is a probability p or a rate r and
     the node sits on eta = log p - log1p(-p) inside where(p > 0, where(p < 1,
     ., -inf), -inf), or theta = log r inside where(r > 0, ., -inf)."""
+    if isinstance(arg, MatVec):
+        if name == "Binomial" or not natural:
+            raise TraceError(f"{name} over X @ beta in its probs= / rate= form (or Binomial): "
+                             "pass the linear predictor as logits= / log_rate=; " + _GLM_FORM)
+        return glm_term(name, arg, value)
+    if any(isinstance(x, MatVec) for x in (value, total)):
+        raise TraceError(f"X @ beta as {name}'s value or total_count: " + _GLM_FORM)
     op = _DISCRETE_OP[name]
     y = _concrete_f32(name, "value", value)
     ey = Expr.of(y)
@@ -907,6 +1053,8 @@ def to_operand(x) -> Operand:
                            transform=xf)
         return Operand(_lib.MC_OP_GATHER, param_offset=x.offset, index=v[1], shape=tuple(v[2]),
                        transform=xf)
+    if isinstance(x, MatVec):
+        raise TraceError("X @ beta as this distribution argument: " + _GLM_FORM)
     if isinstance(x, LogProbExpr):
         raise TraceError("a log density cannot be a distribution argument: " + _UNSUPPORTED)
     if isinstance(x, (Affine, Expr)):
@@ -928,7 +1076,7 @@ def to_operand(x) -> Operand:
 
 
 def is_symbolic(*xs) -> bool:
-    return any(isinstance(x, (Param, LogProbExpr, Affine, Expr)) for x in xs)
+    return any(isinstance(x, (Param, LogProbExpr, Affine, Expr, MatVec)) for x in xs)
 
 
 @dataclass
@@ -945,6 +1093,7 @@ class Term:
     # scale) or ("identity", value) — so a traced or per-element weight can
     # rebuild it as an expression (LogProbExpr._weighted)
     src: Optional[tuple] = None
+    glm: Optional["GlmSpec"] = None                 # GLM_DIST: the design-matrix likelihood
 
 
 def broadcast_n(dist_name: str, ops: List[Operand]) -> Tuple[int, Tuple[int, ...]]:
@@ -1136,7 +1285,7 @@ def identity_expr(x) -> LogProbExpr:
 
 
 def _scaled(t: Term, c: float) -> Term:
-    return Term(t.dist, t.value, t.loc, t.scale, t.n, t.weight * c, t.aff, t.expr, t.src)
+    return Term(t.dist, t.value, t.loc, t.scale, t.n, t.weight * c, t.aff, t.expr, t.src, t.glm)
 
 
 def _term_root(t: Term) -> "Expr":
@@ -1177,6 +1326,11 @@ def _scalar_const(x) -> float:
 
 
 def make_term(dist: int, dist_name: str, value, loc, scale) -> LogProbExpr:
+    if any(isinstance(x, MatVec) for x in (value, loc, scale)):
+        if dist_name != "Normal" or not isinstance(loc, MatVec):
+            raise TraceError(f"X @ beta as an argument of {dist_name} other than Normal's loc: "
+                             + _GLM_FORM)
+        return glm_term("Normal", loc, value, scale)
     if any(isinstance(x, Expr) for x in (value, loc, scale)):
         return dist_expr(dist_name, value, loc, scale)
     try:
@@ -1338,6 +1492,10 @@ class TracedModel:
     c_nodes: object = None
     n_exprs: int = 0
     n_nodes: int = 0
+    # a design-matrix model (mc_program_create_glm): its likelihood, `terms` its
+    # priors, c_glm the mc_glm record addressing the pool `data`
+    glm: Optional["GlmSpec"] = None
+    c_glm: object = None
 
 
 def trace(log_prob_fn, initial_params: dict, keep_order: bool = False) -> TracedModel:
@@ -1355,8 +1513,58 @@ def trace(log_prob_fn, initial_params: dict, keep_order: bool = False) -> Traced
         raise TraceError(f"log_prob must return a scalar (got shape {out.shape}); "
                          "sum the likelihood with mx.sum as the reference does")
     terms = fold_terms(out.terms, adjacent_only=keep_order)
+    if any(t.glm is not None for t in terms):
+        return _glm_model(layout, terms, out.const)
     model = TracedModel(layout, terms, float(np.float32(out.const)))
     _build_pools(model)
+    return model
+
+
+def _glm_model(layout: "ParamLayout", terms: List[Term], const: float) -> TracedModel:
+    """A traced log density with an X @ beta likelihood: exactly one, summed
+    whole, the other terms fused priors on parameters with constant arguments."""
+    like = [t for t in terms if t.glm is not None]
+    if len(like) != 1:
+        raise TraceError("two matvec terms (two X @ beta likelihoods in one log density): "
+                         + _GLM_FORM)
+    if like[0].weight != 1.0:
+        raise TraceError("a weighted X @ beta likelihood (mx.mean, or a constant times it): it "
+                         "is summed whole with mx.sum; " + _GLM_FORM)
+    priors = [t for t in terms if t.glm is None]
+    const_kinds = (_lib.MC_OP_CONST, _lib.MC_OP_NONE)
+    for t in priors:
+        if (t.dist > _lib.MC_DIST_IDENTITY or t.aff is not None
+                or t.value.kind not in (_lib.MC_OP_PSCALAR, _lib.MC_OP_PVEC)
+                or t.loc.kind not in const_kinds or t.scale.kind not in const_kinds):
+            raise TraceError("beside an X @ beta likelihood: a prior with a traced argument, a "
+                             "data likelihood or an expression term; " + _GLM_FORM)
+    spec = like[0].glm
+    model = TracedModel(layout, priors, float(np.float32(const + spec.lp_const)))
+    _build_pools(model)
+    eta = spec.eta
+    N, P = spec.N, spec.P
+    g = _lib.McGlm()
+    g.family, g.beta_offset, g.n, g.p = spec.family, eta.beta[0], N, P
+    g.x_pool, g.y_pool, g.offset_pool = 0, N * P, -1
+    parts = [eta.X.ravel(), spec.y]
+    const_c = float(np.float32(eta.const))
+    off = eta.offset
+    if eta.icpt is not None:
+        g.intercept.kind, g.intercept.param_offset = _lib.MC_OP_PSCALAR, to_operand(
+            eta.icpt).param_offset
+        if const_c != 0.0:  # one intercept operand: a constant beside it joins the offset
+            off = (np.full(N, const_c, np.float32) if off is None
+                   else (off + np.float32(const_c)).astype(np.float32))
+    elif const_c != 0.0:
+        g.intercept.kind, g.intercept.value = _lib.MC_OP_CONST, const_c
+    if off is not None:
+        g.offset_pool = N * P + N
+        parts.append(np.ascontiguousarray(off, np.float32))
+    if spec.scale is not None:
+        g.scale.kind, g.scale.param_offset = spec.scale.kind, spec.scale.param_offset
+        g.scale.value, g.scale.transform = spec.scale.value, spec.scale.transform
+    model.data = np.concatenate(parts).astype(np.float32)
+    model.glm, model.c_glm = spec, g
     return model
 
 
@@ -1500,11 +1708,17 @@ class Program:
         h = ctypes.c_void_p()
         data = np.ascontiguousarray(model.data, np.float32)
         index = np.ascontiguousarray(model.index, np.int32)
-        _lib.check(lib.mc_program_create_expr(
-            model.c_terms, len(model.terms), model.c_affines, model.n_affines, model.c_exprs,
-            model.n_exprs, model.c_nodes, model.n_nodes, self.D,
-            model.lp_const, data.ctypes.data_as(ctypes.c_void_p), data.size,
-            index.ctypes.data_as(ctypes.c_void_p), index.size, ctypes.byref(h)))
+        dp = data.ctypes.data_as(ctypes.c_void_p)
+        if model.glm is not None:
+            _lib.check(lib.mc_program_create_glm(
+                ctypes.byref(model.c_glm), model.c_terms, len(model.terms), self.D,
+                model.lp_const, dp, data.size, ctypes.byref(h)))
+        else:
+            _lib.check(lib.mc_program_create_expr(
+                model.c_terms, len(model.terms), model.c_affines, model.n_affines,
+                model.c_exprs, model.n_exprs, model.c_nodes, model.n_nodes, self.D,
+                model.lp_const, dp, data.size,
+                index.ctypes.data_as(ctypes.c_void_p), index.size, ctypes.byref(h)))
         self.handle = h
         self.waves_per_chain = lib.mc_program_waves_per_chain(h)
         self.num_slices = lib.mc_program_num_slices(h)
@@ -1532,7 +1746,7 @@ class Program:
     def slice_kernel(self) -> str:
         """"unsliced", "interpreter" or "lanes": what an HMC launch will run."""
         k = _lib.load().mc_program_slice_kernel(self.handle)
-        return {0: "unsliced", 1: "interpreter", 2: "lanes"}[k]
+        return {0: "unsliced", 1: "interpreter", 2: "lanes", 3: "glm"}[k]
 
     def nuts_kernel(self, max_tree_depth: int = 10) -> str:
         """"lanes" (k_nuts_lr), "sliced" (k_nuts_sl: a sliced fast-form
@@ -1552,6 +1766,11 @@ class Program:
         if lib.mc_program_nuts_metric_lanes(self.handle, int(max_tree_depth)) == 1:
             return ""
         return (lib.mc_last_error() or b"").decode()
+
+    def glm_slices(self, num_chains: int) -> int:
+        """Row slices per chain block of a design-matrix launch of `num_chains`
+        chains (mc_program_glm_slices; 0 for any other program)."""
+        return int(_lib.load().mc_program_glm_slices(self.handle, int(num_chains)))
 
     @property
     def kernel_note(self) -> str:
@@ -1754,10 +1973,25 @@ def mh_program(prog: "Program") -> "Program":
     return prog
 
 
+def refuse_glm(model: TracedModel, what: str) -> None:
+    """Design-matrix models run under hmc() only: everything else raises before
+    any device work."""
+    if model.glm is not None:
+        raise ValueError(f"{what}: design-matrix (X @ beta) models run under hmc() / "
+                         "MCMC.run(kernel='hmc') without a mass matrix; NUTS, "
+                         "Metropolis-Hastings, the metric and the pointwise / WAIC / LOO / "
+                         "predictive entry points do not take them yet")
+
+
 def compile_model(log_prob_fn, initial_params: dict, slices: int = 0,
-                  slice_kernel: str = "auto") -> Program:
+                  slice_kernel: str = "auto", glm: Optional[str] = None) -> Program:
+    """glm: None where design-matrix models run (hmc()), else the caller's name
+    for the ValueError that refuses them."""
+    model = trace(log_prob_fn, initial_params)
+    if glm is not None:
+        refuse_glm(model, glm)
     _lib.require_device()
-    prog = Program(trace(log_prob_fn, initial_params))
+    prog = Program(model)
     if slices:
         prog.set_slices(slices)
     if slice_kernel != "auto":
@@ -1771,6 +2005,8 @@ def pointwise_program(log_likelihood_fn, layout: ParamLayout) -> Program:
     pointwise view enabled (diagnostics.pointwise_log_likelihood)."""
     _lib.require_device()
     init = {n: np.zeros(shp, np.float32) for n, shp in zip(layout.names, layout.shapes)}
-    prog = Program(trace(log_likelihood_fn, init, keep_order=True))
+    model = trace(log_likelihood_fn, init, keep_order=True)
+    refuse_glm(model, "a pointwise log-likelihood")
+    prog = Program(model)
     prog.enable_pointwise()
     return prog

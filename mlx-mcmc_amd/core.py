@@ -30,7 +30,7 @@ int32 = np.int32
 def array(x, dtype=None):
     if isinstance(x, (list, tuple)) and any(isinstance(v, _trace.LogProbExpr) for v in x):
         return _trace.stack(list(x))
-    if isinstance(x, (_trace.LogProbExpr, _trace.Param, _trace.Affine)):
+    if isinstance(x, (_trace.LogProbExpr, _trace.Param, _trace.Affine, _trace.MatVec)):
         return x
     a = np.asarray(_trace._to_numpy(x))
     if dtype is not None:
@@ -57,6 +57,8 @@ def _as_log_density(x):
 
 
 def sum(x, axis=None, keepdims=False):  # noqa: A001 - mirrors mx.sum
+    if isinstance(x, _trace.MatVec):
+        x._inside()
     if isinstance(x, (_trace.LogProbExpr, _trace.Param, _trace.Affine, _trace.Expr)):
         return _as_log_density(x).sum(axis, keepdims)
     return np.sum(np.asarray(x), axis=axis, keepdims=keepdims)
@@ -65,6 +67,8 @@ def sum(x, axis=None, keepdims=False):  # noqa: A001 - mirrors mx.sum
 def mean(x, axis=None, keepdims=False):
     """mx.mean: of a log density (or a parameter expression summed into one)
     its sum times 1 / n; of concrete arrays the NumPy value."""
+    if isinstance(x, _trace.MatVec):
+        x._inside()
     if isinstance(x, (_trace.LogProbExpr, _trace.Param, _trace.Affine, _trace.Expr)):
         return _as_log_density(x).mean(axis, keepdims)
     return np.mean(np.asarray(_trace._to_numpy(x)), axis=axis, keepdims=keepdims)
@@ -120,6 +124,19 @@ log1p = _elementwise("log1p", _trace._lib.MC_EX_LOG1P, np.log1p)
 tanh = _elementwise("tanh", _trace._lib.MC_EX_TANH, np.tanh)
 sigmoid = _elementwise("sigmoid", _trace._lib.MC_EX_SIGMOID, _sigmoid)
 negative = _elementwise("negative", _trace._lib.MC_EX_NEG, np.negative)
+
+
+def matmul(a, b):
+    """mx.matmul: X @ beta of a data matrix and a traced vector parameter is a
+    design-matrix linear predictor (_trace.MatVec); concrete arrays multiply in
+    NumPy float32."""
+    if _trace.is_symbolic(a, b):
+        if isinstance(b, _trace.Param):
+            return _trace.MatVec.of(a, b)
+        raise _trace.TraceError("mx.matmul of traced values other than (data X, parameter "
+                                "beta): " + _trace._GLM_FORM)
+    return np.matmul(np.asarray(_trace._to_numpy(a), np.float32),
+                     np.asarray(_trace._to_numpy(b), np.float32))
 
 
 def power(a, b):

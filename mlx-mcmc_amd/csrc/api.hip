@@ -49,6 +49,7 @@ extern "C" int mc_logp_grad(const mc_program* p, int64_t n_points, const float* 
     if (n_points == 0) return MC_OK;
     if (!q || !logp || !grad) return fail(MC_ERR_INVALID, "NULL buffer");
     hipStream_t st = (hipStream_t)stream;
+    if (is_glm(p)) return glm_logp_grad(p, n_points, q, logp, grad, st);
     switch (p->wpc) {
         case 1: return p->ex ? launch_logp<1, true>(p, n_points, q, logp, grad, st)
                              : launch_logp<1, false>(p, n_points, q, logp, grad, st);
@@ -224,6 +225,7 @@ extern "C" int mc_state_init(const mc_program* p, int64_t C, const float* q0, do
     if (!p || C < 0 || (C > 0 && (!q0 || !state))) return fail(MC_ERR_INVALID, "bad arguments");
     if (C == 0) return MC_OK;
     hipStream_t st = (hipStream_t)stream;
+    if (is_glm(p)) return glm_state_init(p, C, q0, eps0, state, st);
     switch (p->wpc) {
         case 1: return p->ex ? launch_init<1, true>(p, C, q0, eps0, state, st)
                              : launch_init<1, false>(p, C, q0, eps0, state, st);
@@ -268,6 +270,7 @@ extern "C" int mc_metric_offsets(const mc_program* p, int64_t C, int64_t* minv_o
 extern "C" int mc_metric_init(const mc_program* p, int64_t C, const float* inv_mass, int32_t bcast,
                               void* metric, void* stream) {
     if (!p || C < 0 || (C > 0 && !metric)) return fail(MC_ERR_INVALID, "bad arguments");
+    MC_GLM_REFUSE(p, "mc_metric_init");
     if (C == 0) return MC_OK;
     const int64_t D = p->D;
     hipStream_t st = (hipStream_t)stream;

@@ -150,6 +150,8 @@ struct LanePlan {
     int32_t* d_gidx = nullptr;
 };
 
+struct GlmPlan;  // a design-matrix program (plan_glm.hip, run_glm.hip)
+
 struct mc_program {
     int32_t D = 0;
     float lp_const = 0.0f;
@@ -196,8 +198,32 @@ struct mc_program {
     std::vector<PwSampler> pw_samplers;  // one per pw_term (kind -1: none, every fused term)
     int64_t pw_n_data = 0, pw_n_index = 0;
     void* pw = nullptr;
+    // a design-matrix GLM (mc_program_create_glm): no tape terms, only this plan
+    GlmPlan* glm = nullptr;
 };
 void pw_free(mc_program* p);  // (run_pointwise.hip)
+
+// ---- design-matrix programs (include/mcmc355.h mc_glm) ---------------------------
+// They run mc_logp_grad, mc_state_init and mc_hmc_run on the MFMA kernels of
+// glm.h; every other entry point that takes a program declines them by name.
+inline bool is_glm(const mc_program* p) { return p && p->glm != nullptr; }
+#define MC_GLM_REFUSE(p, what)                                                              \
+    do {                                                                                    \
+        if (is_glm(p))                                                                      \
+            return fail(MC_ERR_UNSUPPORTED, "%s: a design-matrix (X @ beta) program runs "  \
+                        "mc_logp_grad, mc_state_init and mc_hmc_run only", what);          \
+    } while (0)
+void glm_free(mc_program* p);                           // (plan_glm.hip)
+int glm_set_slices(mc_program* p, int32_t S);           // (plan_glm.hip)
+int32_t glm_num_slices(const mc_program* p);            // (plan_glm.hip)
+const char* glm_note(const mc_program* p);              // (plan_glm.hip)
+int64_t glm_hmc_workspace_bytes(const mc_program* p, int64_t C);  // (run_glm.hip)
+int glm_logp_grad(const mc_program* p, int64_t n, const float* q, float* lp, float* g,
+                  hipStream_t st);
+int glm_state_init(const mc_program* p, int64_t C, const float* q0, double eps0, void* state,
+                   hipStream_t st);
+int glm_hmc_run(const mc_program* p, const mc_run_config* cfg, void* state, float* samples,
+                const mc_trace* tr, void* ws, int64_t ws_bytes, hipStream_t st);
 
 inline DevCtx ctx_of(const mc_program* p) {
     DevCtx c;

@@ -291,6 +291,7 @@ static int set_slices(mc_program* p, int32_t S);
 extern "C" int mc_program_set_slices(mc_program* p, int32_t S) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
     if (S < 0 || S > 64) return fail(MC_ERR_INVALID, "num_slices must be in [0, 64]");
+    if (is_glm(p)) return glm_set_slices(p, S);
     free_lanes(p->lrd);
     const int rc = set_slices(p, S);
     // an explicit slice count always runs the program-level kernels
@@ -424,6 +425,7 @@ static int set_slices(mc_program* p, int32_t S) {
 extern "C" int mc_program_set_slice_kernel(mc_program* p, int32_t kernel) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
     if (kernel < 0 || kernel > 2) return fail(MC_ERR_INVALID, "slice kernel must be 0, 1 or 2");
+    MC_GLM_REFUSE(p, "mc_program_set_slice_kernel");
     if (p->sl.S < 2) {
         // an unsliced program: 0 and 2 run it on the lane-resident kernel with
         // one slice (no exchange) — 0 when it qualifies, 2 or an error; 1 keeps
@@ -447,6 +449,7 @@ extern "C" int mc_program_set_slice_kernel(mc_program* p, int32_t kernel) {
 
 extern "C" int32_t mc_program_slice_kernel(const mc_program* p) {
     if (!p) return -1;
+    if (is_glm(p)) return 3;
     // expression terms on the lane layout run there only with their JIT-compiled
     // kernel: without it (off, or its compilation failed) the tape runs them
     if (p->lr.ok && p->lr.has_expr && p->slice_kernel != 1 &&
@@ -478,10 +481,14 @@ extern "C" int32_t mc_program_lane_bundle(const mc_program* p) {
     return p->lr.ok ? p->lr.bundle : 0;
 }
 
-extern "C" int32_t mc_program_num_slices(const mc_program* p) { return p ? p->sl.S : -1; }
+extern "C" int32_t mc_program_num_slices(const mc_program* p) {
+    if (is_glm(p)) return glm_num_slices(p);
+    return p ? p->sl.S : -1;
+}
 
 extern "C" const char* mc_program_kernel_note(const mc_program* p) {
     if (!p) return "";
+    if (is_glm(p)) return glm_note(p);
     const std::string je = jit_error(p);
     if (!je.empty()) {  // (the interpreter runs the expression terms)
         static thread_local std::string buf;
@@ -1276,6 +1283,7 @@ static int lane_plan_host(mc_program* p, int32_t S, SlicePlan& P, bool& sliced) 
     return MC_OK;
 }
 extern "C" int mc_debug_lane_plan_host(mc_program* p, int32_t S) {
+    MC_GLM_REFUSE(p, "mc_debug_lane_plan_host");
     SlicePlan P;
     bool sliced;
     return lane_plan_host(p, S, P, sliced);
@@ -1300,6 +1308,7 @@ template <typename T>
 static uint64_t digest(const std::vector<T>& v) { return fnv1a(v.data(), v.size() * sizeof(T)); }
 extern "C" int mc_debug_plan_digest(mc_program* p, int32_t S, uint64_t* out, int32_t n_out) {
     constexpr int kSlice = 13, kLane = 24;
+    MC_GLM_REFUSE(p, "mc_debug_plan_digest");
     if (!out || n_out < kSlice + kLane) return fail(MC_ERR_INVALID, "out holds %d digests", kSlice + kLane);
     std::fill(out, out + n_out, (uint64_t)0);
     SlicePlan P;
@@ -1335,6 +1344,7 @@ extern "C" int mc_debug_program_host_only(int on) {
 
 extern "C" int mc_program_destroy(mc_program* p) {
     if (!p) return MC_OK;
+    glm_free(p);
     jit_free(p);
     pw_free(p);
     free_slices(p->sl);

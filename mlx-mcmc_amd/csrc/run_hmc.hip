@@ -133,6 +133,7 @@ extern "C" int mc_workspace_status(const mc_program* p, const void* ws, int64_t 
 
 extern "C" int64_t mc_hmc_workspace_bytes(const mc_program* p, int64_t C) {
     if (!p || C < 0) return -1;
+    if (is_glm(p)) return glm_hmc_workspace_bytes(p, C);
     // (a lanes1 program runs L = 0 configurations on the unsliced kernel, and
     // so does a sliced program with transformed operands, which the term
     // interpreter does not take: mc_hmc_run)
@@ -216,6 +217,7 @@ extern "C" int mc_hmc_run(const mc_program* p, const mc_run_config* cfg, void* s
     int rc = hmc_validate(p, cfg, state, false, nullptr);
     if (rc) return rc;
     if (cfg->num_chains == 0 || cfg->iter_count == 0) return MC_OK;
+    if (is_glm(p)) return glm_hmc_run(p, cfg, state, samples, tr, ws, ws_bytes, (hipStream_t)stream);
     if (hmc_exchange_route(p, cfg)) {
         const int64_t need = sl_workspace_bytes(p, cfg->num_chains);
         if (ws == nullptr || ws_bytes < need)
@@ -250,6 +252,7 @@ extern "C" int mc_hmc_run_metric(const mc_program* p, const mc_run_config* cfg, 
                                  void* metric, int32_t adapt, void* stream) {
     int rc = hmc_validate(p, cfg, state, true, metric);
     if (rc) return rc;
+    MC_GLM_REFUSE(p, "mc_hmc_run_metric");
     if (hmc_exchange_route(p, cfg))
         return fail(MC_ERR_UNSUPPORTED,
                     "a metric runs on the chain-per-workgroup kernel k_hmc only and this program "

@@ -48,6 +48,7 @@ extern "C" int mc_mh_run(const mc_program* p, const mc_run_config* cfg, double p
                          int64_t ws_bytes, void* stream) {
     int rc = check_cfg(p, cfg, state);
     if (rc) return rc;
+    MC_GLM_REFUSE(p, "mc_mh_run");
     if (!std::isfinite(proposal_scale)) return fail(MC_ERR_INVALID, "proposal_scale not finite");
     if (cfg->num_chains == 0 || cfg->iter_count == 0) return MC_OK;
     if (use_mh_sliced(p)) {

@@ -177,6 +177,7 @@ static int nuts_validate(const mc_program* p, const mc_run_config* cfg, void* st
                          const void* metric) {
     int rc = check_cfg(p, cfg, state);
     if (rc) return rc;
+    MC_GLM_REFUSE(p, "NUTS");
     if (met && !metric) return fail(MC_ERR_INVALID, "metric buffer is NULL");
     if (cfg->max_tree_depth < 0 || cfg->max_tree_depth > kMaxTreeDepth)
         return fail(MC_ERR_UNSUPPORTED, "max_tree_depth must be in [0, %d]", kMaxTreeDepth);

@@ -43,6 +43,7 @@ extern "C" int64_t mc_program_num_elements(const mc_program* p) {
 
 extern "C" int mc_program_enable_pointwise(mc_program* p) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
+    MC_GLM_REFUSE(p, "the pointwise view (pointwise log-likelihood, WAIC, LOO, predictive)");
     if (p->pw) return MC_OK;
     if (p->host_only)
         return fail(MC_ERR_INVALID, "a host-only program has no device tables");

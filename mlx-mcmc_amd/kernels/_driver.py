@@ -118,8 +118,14 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
             raise ValueError("a mass matrix runs on the chain-per-workgroup kernels: leave "
                              "num_slices at 0 or 1 and slice_kernel at 'auto'")
         num_slices = 1
+    # design-matrix (X @ beta) models run on the GLM kernels under hmc() only
+    glm = None
+    if algorithm == "nuts":
+        glm = "nuts()"
+    elif use_metric:
+        glm = "a mass matrix"
     program = _trace.compile_model(log_prob_fn, initial_params, slices=num_slices,
-                                   slice_kernel=slice_kernel)
+                                   slice_kernel=slice_kernel, glm=glm)
     if algorithm == "nuts" and num_slices == 0 and slice_kernel == "auto" and not use_metric:
         # a large regression's affine terms as expression terms: the sliced
         # NUTS kernel instead of the tape (_trace.nuts_program)
@@ -136,7 +142,8 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
     # structural
     if (algorithm == "hmc" and note and num_slices == 0 and slice_kernel == "auto"
             and program.program_elements >= _LANES_WARN_ELEMENTS
-            and program.model.n_affines == 0 and program.model.n_exprs == 0):
+            and program.model.n_affines == 0 and program.model.n_exprs == 0
+            and program.model.glm is None):
         # a layout the lane-resident kernel declines runs
         # on a 2-4x slower kernel; say so instead of degrading silently
         warnings.warn(f"{note}; running on the {program.slice_kernel} kernel", RuntimeWarning,
@@ -256,6 +263,8 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
                             else program.slice_kernel)
     if note and algorithm == "hmc":
         info.extra["kernel_note"] = note
+    if program.model.glm is not None:
+        info.extra["glm_slices"] = program.glm_slices(C)
     if algorithm == "hmc" and not use_metric and program.hmc_dense:
         # (slices, slots) of the dense route: a chain pair per workgroup
         info.extra["hmc_dense"] = program.hmc_dense

@@ -46,7 +46,8 @@ def metropolis_hastings(log_prob_fn, initial_params, num_samples=1000, proposal_
     k = _as_key(random_seed)
     # (a large regression's affine terms as expression terms: the sliced MH
     # kernel instead of the tape, _trace.mh_program)
-    program = _trace.mh_program(_trace.compile_model(log_prob_fn, initial_params))
+    program = _trace.mh_program(_trace.compile_model(log_prob_fn, initial_params,
+                                                     glm="metropolis_hastings()"))
     layout = program.layout
     C = int(num_chains)
     if C < 1:
