@@ -1168,8 +1168,23 @@ int mc_debug_rank_path(int path);
  * The result is an ordinary mc_program for mc_state_bytes / _offsets / _init,
  * mc_logp_grad, mc_hmc_run / mc_hmc_workspace_bytes, mc_program_set_slices /
  * _num_slices / _kernel_note / _num_params / _destroy (mc_program_slice_kernel
- * returns 3); every other entry point that takes a program returns
- * MC_ERR_UNSUPPORTED (or -1 / 0 where it returns a count).  num_slices here
+ * returns 3) and the pointwise statistics below; every other entry point that
+ * takes a program returns MC_ERR_UNSUPPORTED (or -1 / 0 where it returns a
+ * count).
+ * Pointwise statistics (csrc/glm_pointwise.h).  On a program WITHOUT prior
+ * terms (a likelihood passed alone; with priors: MC_ERR_UNSUPPORTED)
+ * mc_program_enable_pointwise builds the GLM view — the Poisson family's
+ * per-observation normaliser -lgamma(y + 1), float64 rounded once to f32, 0
+ * outside the support, which a pointwise value carries itself (the sampler has
+ * only its sum, in lp_const) — mc_program_num_elements returns N, and
+ * mc_pointwise_workspace_bytes / mc_pointwise_stats keep their arguments,
+ * checks and the six MC_PW_* fields: observation i under draw r is
+ * family(y_i | eta_i(q_r)) formed as the gradient kernel forms it, over all
+ * C * S draws as one FP32 MFMA product that is never stored (a non-NULL
+ * matrix receives [C, S, N]).  The draw blocks depend on (C, S, N) only: two
+ * calls give the same bits, with or without the matrix.  The view is not the
+ * term view of other programs: mc_psis_* and mc_predictive* return
+ * MC_ERR_UNSUPPORTED for a design-matrix program.  num_slices here
  * is row slices per chain block: 0 automatic (enough that slices x chain
  * blocks cover the CUs, at most 64 and at most one 32-row tile per wave),
  * 1..64 that many.  A chain's draws are those of mc_hmc_run on the tape up to

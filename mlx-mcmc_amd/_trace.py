@@ -1974,13 +1974,21 @@ def mh_program(prog: "Program") -> "Program":
 
 
 def refuse_glm(model: TracedModel, what: str) -> None:
-    """Design-matrix models run under hmc() only: everything else raises before
-    any device work."""
+    """Design-matrix models run under hmc() and, as a likelihood alone, under the
+    pointwise / WAIC entry points (pointwise_program): everything else raises
+    before any device work."""
     if model.glm is not None:
         raise ValueError(f"{what}: design-matrix (X @ beta) models run under hmc() / "
-                         "MCMC.run(kernel='hmc') without a mass matrix; NUTS, "
-                         "Metropolis-Hastings, the metric and the pointwise / WAIC / LOO / "
+                         "MCMC.run(kernel='hmc') without a mass matrix, and their "
+                         "likelihood alone under pointwise_log_likelihood / waic; NUTS, "
+                         "Metropolis-Hastings, the metric, PSIS-LOO and the posterior "
                          "predictive entry points do not take them yet")
+
+
+_GLM_POINTWISE_FORM = (
+    "the pointwise log-likelihood of a design-matrix model is exactly one "
+    "mx.sum(Family(X @ beta ...).log_prob(y)), passed alone: priors and other terms belong "
+    "to no observation")
 
 
 def compile_model(log_prob_fn, initial_params: dict, slices: int = 0,
@@ -1999,14 +2007,23 @@ def compile_model(log_prob_fn, initial_params: dict, slices: int = 0,
     return prog
 
 
-def pointwise_program(log_likelihood_fn, layout: ParamLayout) -> Program:
+def pointwise_program(log_likelihood_fn, layout: ParamLayout,
+                      glm: Optional[str] = None) -> Program:
     """A likelihood traced like ``log_prob`` over the parameters of ``layout``,
     its terms in trace order (every element one observation), with the
-    pointwise view enabled (diagnostics.pointwise_log_likelihood)."""
+    pointwise view enabled (diagnostics.pointwise_log_likelihood).  A
+    design-matrix likelihood (one ``mx.sum(Family(X @ beta ...).log_prob(y))``
+    alone: N observations) gets the view of csrc/glm_pointwise.h, which serves
+    the pointwise statistics only — glm: None where that is enough, else the
+    caller's name (LOO, predictive) for the ValueError that refuses it."""
     _lib.require_device()
     init = {n: np.zeros(shp, np.float32) for n, shp in zip(layout.names, layout.shapes)}
     model = trace(log_likelihood_fn, init, keep_order=True)
-    refuse_glm(model, "a pointwise log-likelihood")
+    if glm is not None:
+        refuse_glm(model, glm)
+    if model.glm is not None and model.terms:
+        raise ValueError(f"{len(model.terms)} term(s) beside the X @ beta likelihood: "
+                         + _GLM_POINTWISE_FORM)
     prog = Program(model)
     prog.enable_pointwise()
     return prog

@@ -451,6 +451,9 @@ struct GlmPlan {
     // partials of mc_logp_grad / mc_state_init, which take no workspace: room for
     // kScratchBlocks chain blocks of 64 slices, used in stream order
     float* d_scratch = nullptr;
+    // the pointwise view (run_glm_pointwise.hip): the per-observation normaliser
+    // [Np]; null until mc_program_enable_pointwise
+    float* d_norm = nullptr;
     std::string note;         // the plan in words (mc_program_kernel_note)
 };
 constexpr int kGlmScratchBlocks = 8;

@@ -205,13 +205,15 @@ void pw_free(mc_program* p);  // (run_pointwise.hip)
 
 // ---- design-matrix programs (include/mcmc355.h mc_glm) ---------------------------
 // They run mc_logp_grad, mc_state_init and mc_hmc_run on the MFMA kernels of
-// glm.h; every other entry point that takes a program declines them by name.
+// glm.h and mc_pointwise_stats on that of glm_pointwise.h; every other entry
+// point that takes a program declines them by name.
 inline bool is_glm(const mc_program* p) { return p && p->glm != nullptr; }
 #define MC_GLM_REFUSE(p, what)                                                              \
     do {                                                                                    \
         if (is_glm(p))                                                                      \
             return fail(MC_ERR_UNSUPPORTED, "%s: a design-matrix (X @ beta) program runs "  \
-                        "mc_logp_grad, mc_state_init and mc_hmc_run only", what);          \
+                        "mc_logp_grad, mc_state_init, mc_hmc_run and mc_pointwise_stats only", \
+                        what);                                                              \
     } while (0)
 void glm_free(mc_program* p);                           // (plan_glm.hip)
 int glm_set_slices(mc_program* p, int32_t S);           // (plan_glm.hip)
@@ -224,6 +226,12 @@ int glm_state_init(const mc_program* p, int64_t C, const float* q0, double eps0,
                    hipStream_t st);
 int glm_hmc_run(const mc_program* p, const mc_run_config* cfg, void* state, float* samples,
                 const mc_trace* tr, void* ws, int64_t ws_bytes, hipStream_t st);
+// the pointwise view of a design-matrix program (run_glm_pointwise.hip)
+int64_t glm_pw_elements(const mc_program* p);
+int glm_pw_enable(mc_program* p);
+int64_t glm_pw_workspace_bytes(const mc_program* p, int64_t C, int64_t S);
+int glm_pw_stats(const mc_program* p, int64_t C, int64_t S, const float* samples, double* stats,
+                 float* matrix, void* ws, int64_t ws_bytes, hipStream_t st);
 
 inline DevCtx ctx_of(const mc_program* p) {
     DevCtx c;

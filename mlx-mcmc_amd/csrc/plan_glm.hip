@@ -34,7 +34,7 @@ void glm_free(mc_program* p) {
     GlmPlan* g = p->glm;
     if (!g) return;
     for (void* d : {(void*)g->d_X, (void*)g->d_XT, (void*)g->d_y, (void*)g->d_off,
-                    (void*)g->d_priors, (void*)g->d_scratch})
+                    (void*)g->d_priors, (void*)g->d_scratch, (void*)g->d_norm})
         if (d) (void)hipFree(d);
     delete g;
     p->glm = nullptr;

@@ -1,6 +1,7 @@
 // run_pointwise.hip — the pointwise view of a program and the launches of
 // csrc/pointwise.h (mc_program_num_elements, mc_program_enable_pointwise,
-// mc_pointwise_workspace_bytes, mc_pointwise_stats).
+// mc_pointwise_workspace_bytes, mc_pointwise_stats).  A design-matrix program
+// goes to run_glm_pointwise.hip at each of them.
 #include "host.h"
 #include "pointwise.h"
 #include "pw_view.h"
@@ -38,12 +39,13 @@ void pw_free(mc_program* p) {
 
 extern "C" int64_t mc_program_num_elements(const mc_program* p) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
+    if (is_glm(p)) return glm_pw_elements(p);
     return pw_elements(p);
 }
 
 extern "C" int mc_program_enable_pointwise(mc_program* p) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
-    MC_GLM_REFUSE(p, "the pointwise view (pointwise log-likelihood, WAIC, LOO, predictive)");
+    if (is_glm(p)) return glm_pw_enable(p);  // (its own view: never a PwView)
     if (p->pw) return MC_OK;
     if (p->host_only)
         return fail(MC_ERR_INVALID, "a host-only program has no device tables");
@@ -103,6 +105,7 @@ extern "C" int mc_program_enable_pointwise(mc_program* p) {
 
 extern "C" int64_t mc_pointwise_workspace_bytes(const mc_program* p, int64_t C, int64_t S) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
+    if (is_glm(p)) return glm_pw_workspace_bytes(p, C, S);
     if (C < 1 || S < 1) return fail(MC_ERR_INVALID, "pointwise: C and S must be >= 1");
     const PwView* v = (const PwView*)p->pw;
     if (!v) return fail(MC_ERR_INVALID, "pointwise: call mc_program_enable_pointwise first");
@@ -115,6 +118,8 @@ extern "C" int mc_pointwise_stats(const mc_program* p, int64_t C, int64_t S, con
                                   double* stats, float* matrix, void* ws, int64_t ws_bytes,
                                   void* hip_stream) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
+    if (is_glm(p))
+        return glm_pw_stats(p, C, S, samples, stats, matrix, ws, ws_bytes, (hipStream_t)hip_stream);
     const PwView* v = (const PwView*)p->pw;
     if (!v) return fail(MC_ERR_INVALID, "pointwise: call mc_program_enable_pointwise first");
     if (C < 1 || S < 1) return fail(MC_ERR_INVALID, "pointwise: C and S must be >= 1");

@@ -22,6 +22,10 @@ struct PpPlan {
 };
 int pp_plan(const mc_program* p, int64_t C, int64_t S, int64_t thin, PpPlan* out) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
+    if (is_glm(p))
+        return fail(MC_ERR_UNSUPPORTED, "predictive: a design-matrix (X @ beta) program has "
+                    "pointwise statistics (mc_pointwise_stats) only: the predictive kernels "
+                    "read a term view (PwCtx) and samplers such a program does not have");
     const PwView* v = (const PwView*)p->pw;
     if (!v) return fail(MC_ERR_INVALID, "predictive: call mc_program_enable_pointwise first");
     if (C < 1 || S < 1 || thin < 1)

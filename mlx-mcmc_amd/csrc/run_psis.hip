@@ -14,6 +14,10 @@ struct PsisPlan {
 };
 int psis_plan(const mc_program* p, int64_t C, int64_t S, double r_eff, PsisPlan* out) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
+    if (is_glm(p))
+        return fail(MC_ERR_UNSUPPORTED, "psis: a design-matrix (X @ beta) program has pointwise "
+                    "statistics (mc_pointwise_stats) only: the PSIS kernels read a term view "
+                    "(PwCtx) such a program does not have");
     const PwView* v = (const PwView*)p->pw;
     if (!v) return fail(MC_ERR_INVALID, "psis: call mc_program_enable_pointwise first");
     if (C < 1 || S < 1) return fail(MC_ERR_INVALID, "psis: C and S must be >= 1");

@@ -456,6 +456,12 @@ def pointwise_log_likelihood(log_likelihood_fn, samples, layout=None, *, matrix=
     observation and are left out; nothing guesses which terms of a ``log_prob``
     are observed — pass the likelihood alone.
 
+    A design-matrix likelihood — exactly one
+    ``mx.sum(Family(X @ beta ...).log_prob(y))`` — has N observations, one per
+    row of X, evaluated over all draws as one FP32 MFMA product
+    (csrc/glm_pointwise.h); a Poisson observation carries its own
+    ``-lgamma(y + 1)``.  Other terms beside it raise ``ValueError``.
+
     ``samples``: a [C, S, D] device tensor with its ``layout``, or a dict name
     -> array as ``MCMC.samples`` holds it.  Returns the six statistics
     (``max``, ``sumexp`` = sum exp(x - max), ``n``, ``mean``, ``m2``,
@@ -555,7 +561,7 @@ def loo(log_likelihood_fn, samples, layout=None, *, r_eff=1.0, tail=False, group
         raise ValueError("r_eff must be a positive finite scalar")
     x, lay = _pointwise_inputs(samples, layout)
     C, S, D = x.shape
-    prog = _trace.pointwise_program(log_likelihood_fn, lay)
+    prog = _trace.pointwise_program(log_likelihood_fn, lay, glm="PSIS-LOO (diagnostics.loo)")
     stats, _ = _pointwise_launch(prog, x)
     lib = _lib.load()
     M = prog.num_elements
@@ -692,7 +698,9 @@ def posterior_predictive(log_likelihood_fn, samples, layout=None, *, seed=0, thi
         raise ValueError("thin must be >= 1")
     x, lay = _pointwise_inputs(samples, layout)
     C, S, D = x.shape
-    prog = _trace.pointwise_program(log_likelihood_fn, lay)
+    prog = _trace.pointwise_program(log_likelihood_fn, lay,
+                                    glm="posterior predictive replicates "
+                                        "(diagnostics.posterior_predictive)")
     lib = _lib.load()
     M = prog.num_elements
     nb = lib.mc_predictive_workspace_bytes(prog.handle, C, S, thin)
