@@ -1215,6 +1215,34 @@ int mc_program_create_glm(const mc_glm* glm, const mc_term* priors, int32_t n_pr
 int32_t mc_program_glm_slices(const mc_program* prog, int64_t num_chains);
 int32_t mc_program_glm_chain_block(const mc_program* prog);
 
+/* NUTS of a design-matrix program (csrc/glm_nuts.h): mc_nuts_run's config,
+ * state, samples, trace and draw addressing, on mc_nuts_glm_workspace_bytes
+ * bytes of device memory (-1 for any other program or a max_tree_depth outside
+ * [0, 16]).  A tick is one gradient launch at every chain's pending position
+ * and one tree step; every chain carries its own iteration number and tree
+ * state through the ticks, so a window costs the largest per-chain total of
+ * leaves.  The host cannot know that number: it enqueues ticks in batches and
+ * after each reads the device's count of chains still running through a pinned
+ * host word the program owns.  UNLIKE EVERY OTHER ENTRY, THIS ONE SYNCHRONISES
+ * THE STREAM INSIDE THE CALL (once per batch) and cannot be captured into a
+ * graph; calls on one program must be ordered on one stream.  It returns
+ * MC_ERR_UNSUPPORTED for a program that is not a design-matrix program or a
+ * max_tree_depth outside [0, 16], MC_ERR_INVALID for a NULL or short
+ * workspace, each before any launch, and MC_ERR_TIMEOUT (an internal error)
+ * if chains are left after the iter_count * 2^max_tree_depth ticks no window
+ * can need.  mc_nuts_run keeps declining design-matrix programs.  A global
+ * chain's draws are the same bytes for any split of the chains over calls
+ * (chain_offset), chain blocks and GPUs and any cut of the run into windows,
+ * at a fixed slice count.                                                    */
+int64_t mc_nuts_glm_workspace_bytes(const mc_program* prog, int64_t num_chains,
+                                    int32_t max_tree_depth);
+int mc_nuts_run_glm(const mc_program* prog, const mc_run_config* cfg,
+                    void* state_dev, float* samples_dev, const mc_trace* trace,
+                    void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+/* Measurement hook: the ticks enqueued and host polls of mc_nuts_run_glm since
+ * the last call (either pointer may be NULL); resets both.                    */
+int mc_debug_glm_nuts_stats(int64_t* ticks, int64_t* polls);
+
 const char* mc_last_error(void);
 int32_t mc_abi_version(void);
 

@@ -251,6 +251,25 @@ class ChainSet:
             ctypes.byref(tr) if tr is not None else None, _lib.ptr(ws),
             ws.numel() if ws is not None else 0, _lib.stream_handle()))
 
+    def run_nuts_glm(self, *, samples=None, trace: Optional[Trace] = None, **cfg):
+        """NUTS iterations of a design-matrix program (mc_nuts_run_glm, csrc/glm_nuts.h).
+        Unlike the other launches this one synchronises the stream: the host enqueues
+        batches of gradient + tree-step launches until the device reports every chain
+        through the window."""
+        c = self._config(**cfg)
+        need = self.lib.mc_nuts_glm_workspace_bytes(self.program.handle, self.C,
+                                                    c.max_tree_depth)
+        if need < 0:
+            raise _lib.EngineError(_lib.MC_ERR_UNSUPPORTED,
+                                   "mc_nuts_run_glm takes design-matrix programs and "
+                                   f"max_tree_depth in [0, 16], not {c.max_tree_depth}")
+        ws = self._workspace(need)
+        tr = trace.c_struct() if trace is not None else None
+        _lib.check(self.lib.mc_nuts_run_glm(
+            self.program.handle, ctypes.byref(c), _lib.ptr(self.state), _lib.ptr(samples),
+            ctypes.byref(tr) if tr is not None else None, _lib.ptr(ws),
+            ws.numel() if ws is not None else 0, _lib.stream_handle()))
+
     def run_nuts_metric(self, *, adapt: bool = False, samples=None,
                         trace: Optional[Trace] = None, **cfg):
         """``run_nuts`` with the metric of ``set_metric`` (mc_nuts_run_metric)."""

@@ -315,6 +315,12 @@ SIGNATURES = [
     ("mc_nuts_run", ctypes.c_int,
      [_VP, ctypes.POINTER(McRunConfig), _VP, _VP, ctypes.POINTER(McTrace), _VP,
       ctypes.c_int64, _VP]),
+    ("mc_nuts_glm_workspace_bytes", ctypes.c_int64, [_VP, ctypes.c_int64, ctypes.c_int32]),
+    ("mc_nuts_run_glm", ctypes.c_int,
+     [_VP, ctypes.POINTER(McRunConfig), _VP, _VP, ctypes.POINTER(McTrace), _VP,
+      ctypes.c_int64, _VP]),
+    ("mc_debug_glm_nuts_stats", ctypes.c_int,
+     [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     ("mc_metric_schedule", ctypes.c_int32,
      [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]),
     ("mc_metric_bytes", ctypes.c_int64, [_VP, ctypes.c_int64]),

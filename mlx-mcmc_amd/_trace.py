@@ -1982,7 +1982,9 @@ def refuse_glm(model: TracedModel, what: str) -> None:
                          "MCMC.run(kernel='hmc') without a mass matrix, and their "
                          "likelihood alone under pointwise_log_likelihood / waic; NUTS, "
                          "Metropolis-Hastings, the metric, PSIS-LOO and the posterior "
-                         "predictive entry points do not take them yet")
+                         "predictive entry points do not take them yet (NUTS does when asked "
+                         "to: nuts(..., nuts_kernel='glm') / MCMC.run(method='nuts', "
+                         "nuts_kernel='glm'))")
 
 
 _GLM_POINTWISE_FORM = (
@@ -1992,12 +1994,19 @@ _GLM_POINTWISE_FORM = (
 
 
 def compile_model(log_prob_fn, initial_params: dict, slices: int = 0,
-                  slice_kernel: str = "auto", glm: Optional[str] = None) -> Program:
+                  slice_kernel: str = "auto", glm: Optional[str] = None,
+                  require_glm: Optional[str] = None) -> Program:
     """glm: None where design-matrix models run (hmc()), else the caller's name
-    for the ValueError that refuses them."""
+    for the ValueError that refuses them.  require_glm: the caller's name where
+    only design-matrix models run (nuts(nuts_kernel="glm")), for the ValueError
+    that refuses any other model."""
     model = trace(log_prob_fn, initial_params)
     if glm is not None:
         refuse_glm(model, glm)
+    if require_glm is not None and model.glm is None:
+        raise ValueError(f"{require_glm} runs design-matrix models only: a likelihood "
+                         "Family(X @ beta [+ intercept] [+ offset]) of the Normal, Bernoulli "
+                         "(logits) or Poisson (log_rate) family with priors on its parameters")
     _lib.require_device()
     prog = Program(model)
     if slices:

@@ -454,6 +454,9 @@ struct GlmPlan {
     // the pointwise view (run_glm_pointwise.hip): the per-observation normaliser
     // [Np]; null until mc_program_enable_pointwise
     float* d_norm = nullptr;
+    // mc_nuts_run_glm's count of chains still running, read after every batch of
+    // ticks: one pinned host word, allocated with the program
+    int32_t* h_left = nullptr;
     std::string note;         // the plan in words (mc_program_kernel_note)
 };
 constexpr int kGlmScratchBlocks = 8;
@@ -464,3 +467,7 @@ inline int64_t glm_block_floats(const GlmPlan* g) {
 }
 // row slices of a launch of C chains (plan_glm.hip)
 int glm_plan_slices(const GlmPlan* g, int64_t C);
+// k_glm_grad at the positions q (strides sc, sp: above) of C chains, S slices
+// (run_glm.hip)
+int glm_launch_grad(const GlmPlan* g, const float* q, int sc, int sp, int64_t C, int S, float* part,
+                    hipStream_t st);

@@ -36,6 +36,7 @@ void glm_free(mc_program* p) {
     for (void* d : {(void*)g->d_X, (void*)g->d_XT, (void*)g->d_y, (void*)g->d_off,
                     (void*)g->d_priors, (void*)g->d_scratch, (void*)g->d_norm})
         if (d) (void)hipFree(d);
+    if (g->h_left) (void)hipHostFree(g->h_left);
     delete g;
     p->glm = nullptr;
 }
@@ -192,6 +193,8 @@ extern "C" int mc_program_create_glm(const mc_glm* glm, const mc_term* priors, i
         hipMalloc((void**)&g->d_scratch, (size_t)kGlmMaxSlices * kGlmScratchBlocks *
                                              glm_block_floats(g) * 4) != hipSuccess)
         rc = fail(MC_ERR_NOMEM, "device allocation of the GLM scratch failed");
+    if (rc == MC_OK && hipHostMalloc((void**)&g->h_left, 64, hipHostMallocDefault) != hipSuccess)
+        rc = fail(MC_ERR_NOMEM, "pinned host allocation of the GLM NUTS counter failed");
     if (rc != MC_OK) {
         const std::string err = g_last_error;
         mc_program_destroy(p);

@@ -89,6 +89,11 @@ static int glm_eval(const mc_program* p, int64_t n, const float* q, float* lp, f
     return MC_OK;
 }
 
+int glm_launch_grad(const GlmPlan* g, const float* q, int sc, int sp, int64_t C, int S, float* part,
+                    hipStream_t st) {
+    return launch_grad(g, q, sc, sp, C, S, part, st);
+}
+
 int glm_logp_grad(const mc_program* p, int64_t n, const float* q, float* lp, float* g,
                   hipStream_t st) {
     return glm_eval<false>(p, n, q, lp, g, 0.0, nullptr, nullptr, st);

@@ -118,15 +118,22 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
             raise ValueError("a mass matrix runs on the chain-per-workgroup kernels: leave "
                              "num_slices at 0 or 1 and slice_kernel at 'auto'")
         num_slices = 1
-    # design-matrix (X @ beta) models run on the GLM kernels under hmc() only
+    # design-matrix (X @ beta) models run on the GLM kernels under hmc() and,
+    # opted in, under nuts(nuts_kernel="glm") (csrc/glm_nuts.h)
+    nuts_glm = algorithm == "nuts" and nuts_kernel == "glm"
+    if nuts_glm and use_metric:
+        raise ValueError("nuts_kernel='glm' runs design-matrix (X @ beta) models without a mass "
+                         "matrix: the metric has no kernel on the GLM layout")
     glm = None
-    if algorithm == "nuts":
+    if algorithm == "nuts" and not nuts_glm:
         glm = "nuts()"
     elif use_metric:
         glm = "a mass matrix"
     program = _trace.compile_model(log_prob_fn, initial_params, slices=num_slices,
-                                   slice_kernel=slice_kernel, glm=glm)
-    if algorithm == "nuts" and num_slices == 0 and slice_kernel == "auto" and not use_metric:
+                                   slice_kernel=slice_kernel, glm=glm,
+                                   require_glm="nuts_kernel='glm'" if nuts_glm else None)
+    if (algorithm == "nuts" and num_slices == 0 and slice_kernel == "auto" and not use_metric
+            and not nuts_glm):
         # a large regression's affine terms as expression terms: the sliced
         # NUTS kernel instead of the tape (_trace.nuts_program)
         program = _trace.nuts_program(program, max_tree_depth)
@@ -171,7 +178,7 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
     else:
         cfg["max_tree_depth"] = max_tree_depth
         cfg["slice_mode"] = {"reference": 0, "exact": 1}[slice_mode]
-        launch = chains.run_nuts
+        launch = chains.run_nuts_glm if nuts_glm else chains.run_nuts
         if use_metric:
             launch = functools.partial(
                 chains.run_nuts_metric_lanes if metric_lanes else chains.run_nuts_metric,
@@ -259,8 +266,8 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
         n_divergent=(s["n_divergent"].copy() if algorithm == "nuts" else None),
         trace=trace.numpy() if trace is not None else None,
         device_samples=flat if keep_on_device else None, layout=layout)
-    info.extra["kernel"] = (program.nuts_kernel(max_tree_depth) if algorithm == "nuts"
-                            else program.slice_kernel)
+    info.extra["kernel"] = ("glm" if nuts_glm else program.nuts_kernel(max_tree_depth)
+                            if algorithm == "nuts" else program.slice_kernel)
     if note and algorithm == "hmc":
         info.extra["kernel_note"] = note
     if program.model.glm is not None:

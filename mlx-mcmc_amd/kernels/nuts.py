@@ -17,7 +17,15 @@ row), else ``k_nuts``; "tape" keeps ``k_nuts``; "lanes" is accepted with a mass
 matrix only (below: the metric on ``k_nuts_lr``, or a ``ValueError``) — without one
 it raises ``ValueError`` before anything is traced, as an unknown value does
 ("auto" already picks ``k_nuts_lr`` where the model plans onto it).
-``num_slices``: data slices per chain (0: the automatic plan, as ``hmc()``).
+``"glm"`` runs a design-matrix model (``X @ beta`` under a Normal, Bernoulli-logit
+or Poisson-log likelihood, the models ``hmc()`` runs on the MFMA gradient kernel)
+on that kernel with the tree step ``k_glm_nuts_step`` (csrc/glm_nuts.h): every
+leaf of every chain's tree is one column of a batched gradient launch, and the
+chains of a block walk their trees independently of each other; any other model,
+or a mass matrix, raises ``ValueError``.  Without the option ``nuts()`` declines
+design-matrix models, as before.
+``num_slices``: data slices per chain (0: the automatic plan, as ``hmc()``); with
+``nuts_kernel="glm"`` row slices per chain block, as ``hmc()`` takes them.
 
 ``slice_mode="reference"`` (default) reproduces the reference's float32
 slice variable: u = f32 exp(log u) rounds to the smallest denormal (log u =
@@ -56,8 +64,9 @@ def nuts(log_prob_fn, initial_params, num_samples=1000, num_warmup=1000, step_si
     is the fraction of sampling iterations whose mean acceptance statistic
     exceeds 0.5 (nuts.py:347).
     """
-    if nuts_kernel not in ("auto", "tape", "lanes"):
-        raise ValueError(f"nuts_kernel must be 'auto', 'tape' or 'lanes', not {nuts_kernel!r}")
+    if nuts_kernel not in ("auto", "tape", "lanes", "glm"):
+        raise ValueError("nuts_kernel must be 'auto', 'tape' or 'lanes' (or 'glm' for a "
+                         f"design-matrix model), not {nuts_kernel!r}")
     if nuts_kernel == "lanes" and inverse_mass_matrix is None and not adapt_mass_matrix:
         raise ValueError("nuts_kernel='lanes' chooses the kernel of a run with a mass matrix: "
                          "pass inverse_mass_matrix= or adapt_mass_matrix=True with it. Without "
