@@ -1164,7 +1164,8 @@ int mc_debug_rank_path(int path);
  * unused) loc and scale; anything else is MC_ERR_UNSUPPORTED.
  * Limits, each MC_ERR_UNSUPPORTED before any device work: 1 <= P <=
  * MC_GLM_MAX_P (the gradient block of 32 chains lives in accumulator
- * registers, 16 per 32 coefficients), N >= 1, the padded N * P below 2^31.
+ * registers, 16 per 32 coefficients; mc_program_create_glm_wide below takes
+ * up to MC_GLM_WIDE_MAX_P), N >= 1, the padded N * P below 2^31.
  * The result is an ordinary mc_program for mc_state_bytes / _offsets / _init,
  * mc_logp_grad, mc_hmc_run / mc_hmc_workspace_bytes, mc_program_set_slices /
  * _num_slices / _kernel_note / _num_params / _destroy (mc_program_slice_kernel
@@ -1214,6 +1215,24 @@ int mc_program_create_glm(const mc_glm* glm, const mc_term* priors, int32_t n_pr
  * (the MFMA tile's N dimension, 32).                                        */
 int32_t mc_program_glm_slices(const mc_program* prog, int64_t num_chains);
 int32_t mc_program_glm_chain_block(const mc_program* prog);
+/* The same program on the column-split gradient kernel (csrc/glm_wide.h): the
+ * arguments, checks, limits and result of mc_program_create_glm, with 1 <= P <=
+ * MC_GLM_WIDE_MAX_P (MC_ERR_UNSUPPORTED above it, before any device work).  The
+ * four waves of a workgroup share its row tiles and each holds a quarter of the
+ * gradient block's columns: P is padded to 128 x one of 1, 2, 3, 4, 6, 8, a lane
+ * holds 16 accumulator registers per 128 padded columns, and above 256 padded
+ * columns the coefficients pass through LDS in chunks of 256 rows
+ * (mc_program_kernel_note says which).  Every entry that takes a program of
+ * mc_program_create_glm takes this one, mc_nuts_run_glm included, with the same
+ * guarantees (a chain's draws do not depend on the split of the chains; two
+ * calls give the same bits) — except mc_program_enable_pointwise, which returns
+ * MC_ERR_UNSUPPORTED: the pointwise kernel has the cap of MC_GLM_MAX_P.  The
+ * gradient's sums run in another order than on a program of
+ * mc_program_create_glm: the two agree to fp32 rounding, not in bits.        */
+#define MC_GLM_WIDE_MAX_P      1024
+int mc_program_create_glm_wide(const mc_glm* glm, const mc_term* priors, int32_t n_priors,
+                               int32_t n_params, float lp_const,
+                               const float* data, int64_t n_data, mc_program** out);
 
 /* NUTS of a design-matrix program (csrc/glm_nuts.h): mc_nuts_run's config,
  * state, samples, trace and draw addressing, on mc_nuts_glm_workspace_bytes

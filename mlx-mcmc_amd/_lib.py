@@ -150,6 +150,7 @@ class McExpr(ctypes.Structure):
 # mc_glm families (design-matrix programs, mc_program_create_glm)
 MC_GLM_NORMAL, MC_GLM_BERNOULLI_LOGIT, MC_GLM_POISSON_LOG = range(3)
 MC_GLM_MAX_P = 256
+MC_GLM_WIDE_MAX_P = 1024  # mc_program_create_glm_wide (csrc/glm_wide.h)
 
 
 class McGlm(ctypes.Structure):
@@ -244,6 +245,9 @@ SIGNATURES = [
       ctypes.c_int32, ctypes.c_float, _VP, ctypes.c_int64, _VP, ctypes.c_int64,
       ctypes.POINTER(_VP)]),
     ("mc_program_create_glm", ctypes.c_int,
+     [ctypes.POINTER(McGlm), ctypes.POINTER(McTerm), ctypes.c_int32, ctypes.c_int32,
+      ctypes.c_float, _VP, ctypes.c_int64, ctypes.POINTER(_VP)]),
+    ("mc_program_create_glm_wide", ctypes.c_int,
      [ctypes.POINTER(McGlm), ctypes.POINTER(McTerm), ctypes.c_int32, ctypes.c_int32,
       ctypes.c_float, _VP, ctypes.c_int64, ctypes.POINTER(_VP)]),
     ("mc_program_glm_slices", ctypes.c_int32, [_VP, ctypes.c_int64]),

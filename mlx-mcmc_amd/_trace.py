@@ -1700,9 +1700,12 @@ def _linearize(root: Expr, n: int) -> List[tuple]:
 class Program:
     """An mc_program handle owning its device copy of the model."""
 
-    def __init__(self, model: TracedModel):
+    def __init__(self, model: TracedModel, glm_kernel: str = "auto"):
+        """glm_kernel: "auto", or "wide" for a design-matrix model on the
+        column-split gradient kernel (mc_program_create_glm_wide)."""
         lib = _lib.load()
         self.model = model
+        self.glm_kernel = glm_kernel
         self.layout = model.layout
         self.D = model.layout.size
         h = ctypes.c_void_p()
@@ -1710,7 +1713,9 @@ class Program:
         index = np.ascontiguousarray(model.index, np.int32)
         dp = data.ctypes.data_as(ctypes.c_void_p)
         if model.glm is not None:
-            _lib.check(lib.mc_program_create_glm(
+            create = (lib.mc_program_create_glm_wide if glm_kernel == "wide"
+                      else lib.mc_program_create_glm)
+            _lib.check(create(
                 ctypes.byref(model.c_glm), model.c_terms, len(model.terms), self.D,
                 model.lp_const, dp, data.size, ctypes.byref(h)))
         else:
@@ -1993,22 +1998,32 @@ _GLM_POINTWISE_FORM = (
     "to no observation")
 
 
+def check_glm_kernel(glm_kernel: str) -> None:
+    if glm_kernel not in ("auto", "wide"):
+        raise ValueError(f"glm_kernel must be 'auto' or 'wide', not {glm_kernel!r}")
+
+
 def compile_model(log_prob_fn, initial_params: dict, slices: int = 0,
                   slice_kernel: str = "auto", glm: Optional[str] = None,
-                  require_glm: Optional[str] = None) -> Program:
+                  require_glm: Optional[str] = None, glm_kernel: str = "auto") -> Program:
     """glm: None where design-matrix models run (hmc()), else the caller's name
     for the ValueError that refuses them.  require_glm: the caller's name where
     only design-matrix models run (nuts(nuts_kernel="glm")), for the ValueError
-    that refuses any other model."""
+    that refuses any other model.  glm_kernel: "auto", or "wide" for a
+    design-matrix model on the column-split gradient kernel k_glm_grad_wide
+    (csrc/glm_wide.h: up to 1024 columns); any other model is a ValueError."""
+    check_glm_kernel(glm_kernel)
     model = trace(log_prob_fn, initial_params)
     if glm is not None:
         refuse_glm(model, glm)
+    if glm_kernel == "wide" and require_glm is None:
+        require_glm = "glm_kernel='wide'"
     if require_glm is not None and model.glm is None:
         raise ValueError(f"{require_glm} runs design-matrix models only: a likelihood "
                          "Family(X @ beta [+ intercept] [+ offset]) of the Normal, Bernoulli "
                          "(logits) or Poisson (log_rate) family with priors on its parameters")
     _lib.require_device()
-    prog = Program(model)
+    prog = Program(model, glm_kernel)
     if slices:
         prog.set_slices(slices)
     if slice_kernel != "auto":

@@ -26,7 +26,9 @@
 //              register feeds one MFMA per 32-wide coefficient tile with A =
 //              X[those two rows][tile + l % 32] from the row-major X: no
 //              shuffle, no LDS.  G stays in PT x 16 accumulator registers per
-//              lane for the whole launch (PT = Pp / 32 <= 8: P <= 256).
+//              lane for the whole launch (PT = Pp / 32 <= 8: P <= 256;
+//              glm_wide.h splits G's columns over the waves instead and
+//              takes P <= 1024 on the same partial block).
 //   output     the waves add G through LDS in wave order (the coefficient
 //              buffer, free by then) and the workgroup writes one partial
 //              block [Pp + 4][32] to its slot (slice, chain block): rows Pp,
@@ -447,6 +449,10 @@ struct GlmPlan {
     float *d_X = nullptr, *d_XT = nullptr, *d_y = nullptr, *d_off = nullptr;
     mc::GlmPrior* d_priors = nullptr;
     int PT = 1;               // 32-wide coefficient tiles: 1, 2, 4 or 8
+    // mc_program_create_glm_wide: the gradient runs on k_glm_grad_wide (glm_wide.h),
+    // every wave owning PTW 32-wide coefficient tiles: Pp = 128 PTW, PT = 4 PTW
+    bool wide = false;
+    int PTW = 0;
     int slices = 0;           // mc_program_set_slices: 0 automatic, else 1 .. 64
     // partials of mc_logp_grad / mc_state_init, which take no workspace: room for
     // kScratchBlocks chain blocks of 64 slices, used in stream order
@@ -467,7 +473,7 @@ inline int64_t glm_block_floats(const GlmPlan* g) {
 }
 // row slices of a launch of C chains (plan_glm.hip)
 int glm_plan_slices(const GlmPlan* g, int64_t C);
-// k_glm_grad at the positions q (strides sc, sp: above) of C chains, S slices
-// (run_glm.hip)
+// k_glm_grad, or k_glm_grad_wide on a wide plan, at the positions q (strides sc,
+// sp: above) of C chains, S slices (run_glm.hip)
 int glm_launch_grad(const GlmPlan* g, const float* q, int sc, int sp, int64_t C, int S, float* part,
                     hipStream_t st);

@@ -20,7 +20,19 @@ int glm_plan_slices(const GlmPlan* g, int64_t C) {
 
 static void glm_describe(GlmPlan* g) {
     static const char* fam[] = {"normal", "bernoulli-logit", "poisson-log"};
-    char buf[320];
+    char buf[400];
+    if (g->wide) {
+        std::snprintf(buf, sizeof buf,
+                      "design-matrix GLM (%s): N = %d, P = %d on k_glm_grad_wide / k_glm_hmc_step: 32 "
+                      "chains per block, %d columns per wave (%d coefficient tile%s of 32, %d "
+                      "accumulator registers per lane), coefficients %s, %s row slices per chain "
+                      "block", fam[g->dev.family], g->dev.N, g->dev.P, 32 * g->PTW, g->PTW,
+                      g->PTW == 1 ? "" : "s", 16 * g->PTW,
+                      g->dev.Pp > 256 ? "staged in chunks of 256 rows" : "resident in LDS",
+                      g->slices > 0 ? std::to_string(g->slices).c_str() : "automatic");
+        g->note = buf;
+        return;
+    }
     std::snprintf(buf, sizeof buf,
                   "design-matrix GLM (%s): N = %d, P = %d on k_glm_grad / k_glm_hmc_step: 32 chains "
                   "per block, %d coefficient tile%s of 32 (%d accumulator registers per lane), %s "
@@ -69,9 +81,17 @@ static int upload(const std::vector<T>& h, T** d) {
     return MC_OK;
 }
 
-extern "C" int mc_program_create_glm(const mc_glm* glm, const mc_term* priors, int32_t n_priors,
-                                     int32_t n_params, float lp_const, const float* data,
-                                     int64_t n_data, mc_program** out) {
+// PTW of a wide plan: the first instantiation of k_glm_grad_wide (run_glm.hip)
+// whose 128 PTW columns hold P
+static int wide_ptw(int64_t P) {
+    for (int ptw : {1, 2, 3, 4, 6, 8})
+        if (128 * ptw >= P) return ptw;
+    return 0;
+}
+
+static int create_glm(bool wide, const mc_glm* glm, const mc_term* priors, int32_t n_priors,
+                      int32_t n_params, float lp_const, const float* data, int64_t n_data,
+                      mc_program** out) {
     if (!glm || !out) return fail(MC_ERR_INVALID, "NULL glm / out");
     if (n_params < 1) return fail(MC_ERR_INVALID, "n_params must be >= 1");
     if (n_priors < 0 || (n_priors > 0 && !priors)) return fail(MC_ERR_INVALID, "priors");
@@ -80,13 +100,21 @@ extern "C" int mc_program_create_glm(const mc_glm* glm, const mc_term* priors, i
         return fail(MC_ERR_INVALID, "unknown GLM family %d", glm->family);
     const int64_t N = glm->n, P = glm->p;
     if (N < 1 || P < 1) return fail(MC_ERR_INVALID, "a design matrix needs N >= 1 and P >= 1");
-    if (P > MC_GLM_MAX_P)
+    if (wide && P > MC_GLM_WIDE_MAX_P)
+        return fail(MC_ERR_UNSUPPORTED,
+                    "design-matrix GLM on the column-split kernel: P = %lld columns, at most %d "
+                    "(a wave holds a quarter of the gradient of a block of 32 chains in accumulator "
+                    "registers, 16 per 32 coefficients)", (long long)P, MC_GLM_WIDE_MAX_P);
+    if (!wide && P > MC_GLM_MAX_P)
         return fail(MC_ERR_UNSUPPORTED,
                     "design-matrix GLM: P = %lld columns, at most %d (the gradient of a block of 32 "
-                    "chains lives in accumulator registers, 16 per 32 coefficients)", (long long)P,
-                    MC_GLM_MAX_P);
+                    "chains lives in accumulator registers, 16 per 32 coefficients); "
+                    "mc_program_create_glm_wide (glm_kernel=\"wide\") splits the columns over the "
+                    "waves and takes up to %d", (long long)P, MC_GLM_MAX_P, MC_GLM_WIDE_MAX_P);
+    const int PTW = wide ? wide_ptw(P) : 0;
     int PT = 1;
     while (32 * PT < P) PT *= 2;
+    if (wide) PT = 4 * PTW;
     const int64_t Np = (N + 31) / 32 * 32, Pp = 32 * PT;
     if (Np * Pp >= ((int64_t)1 << 31))
         return fail(MC_ERR_UNSUPPORTED,
@@ -165,6 +193,8 @@ extern "C" int mc_program_create_glm(const mc_glm* glm, const mc_term* priors, i
     GlmPlan* g = new GlmPlan();
     p->glm = g;
     g->PT = PT;
+    g->wide = wide;
+    g->PTW = PTW;
     GlmDev& d = g->dev;
     d.family = glm->family;
     d.N = (int32_t)N;
@@ -209,4 +239,16 @@ extern "C" int mc_program_create_glm(const mc_glm* glm, const mc_term* priors, i
     glm_describe(g);
     *out = p;
     return MC_OK;
+}
+
+extern "C" int mc_program_create_glm(const mc_glm* glm, const mc_term* priors, int32_t n_priors,
+                                     int32_t n_params, float lp_const, const float* data,
+                                     int64_t n_data, mc_program** out) {
+    return create_glm(false, glm, priors, n_priors, n_params, lp_const, data, n_data, out);
+}
+
+extern "C" int mc_program_create_glm_wide(const mc_glm* glm, const mc_term* priors, int32_t n_priors,
+                                          int32_t n_params, float lp_const, const float* data,
+                                          int64_t n_data, mc_program** out) {
+    return create_glm(true, glm, priors, n_priors, n_params, lp_const, data, n_data, out);
 }

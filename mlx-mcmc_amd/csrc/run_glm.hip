@@ -1,5 +1,6 @@
 // run_glm.hip — launches of the design-matrix kernels (glm.h): mc_logp_grad,
-// mc_state_init and mc_hmc_run of a program made by mc_program_create_glm.
+// mc_state_init and mc_hmc_run of a program made by mc_program_create_glm or
+// mc_program_create_glm_wide (the gradient then runs on glm_wide.h's kernel).
 //
 // mc_hmc_run enqueues, per iteration, one k_glm_hmc_step for the iteration
 // start, then per leapfrog step one k_glm_grad and one k_glm_hmc_step, in stream
@@ -9,7 +10,7 @@
 // gradient for its first half kick: L gradient launches and L + 1 step
 // launches.  No host synchronisation and no allocation inside the call.
 #include "launch.h"
-#include "glm.h"
+#include "glm_wide.h"
 
 static int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
@@ -54,9 +55,40 @@ static int launch_grad_fam(const GlmPlan* g, const float* q, int sc, int sp, int
         default: return launch_grad_pt<FAM, 8>(g, q, sc, sp, C, S, part, st);
     }
 }
-// k_glm_grad at the positions q (strides sc, sp: glm.h) of C chains, S slices
+template <int FAM, int PTW>
+static int launch_wide_ptw(const GlmPlan* g, const float* q, int sc, int sp, int64_t C, int S,
+                           float* part, hipStream_t st) {
+    const int64_t blocks = (C + kGlmChains - 1) / kGlmChains;
+    hipLaunchKernelGGL((k_glm_grad_wide<FAM, PTW>), dim3((unsigned)S, (unsigned)blocks), dim3(256), 0,
+                       st, g->dev, q, sc, sp, C, S, part);
+    MC_HIP_TRY(hipGetLastError());
+    return MC_OK;
+}
+template <int FAM>
+static int launch_wide_fam(const GlmPlan* g, const float* q, int sc, int sp, int64_t C, int S,
+                           float* part, hipStream_t st) {
+    switch (g->PTW) {
+        case 1: return launch_wide_ptw<FAM, 1>(g, q, sc, sp, C, S, part, st);
+        case 2: return launch_wide_ptw<FAM, 2>(g, q, sc, sp, C, S, part, st);
+        case 3: return launch_wide_ptw<FAM, 3>(g, q, sc, sp, C, S, part, st);
+        case 4: return launch_wide_ptw<FAM, 4>(g, q, sc, sp, C, S, part, st);
+        case 6: return launch_wide_ptw<FAM, 6>(g, q, sc, sp, C, S, part, st);
+        case 8: return launch_wide_ptw<FAM, 8>(g, q, sc, sp, C, S, part, st);
+        default: return fail(MC_ERR_INVALID, "k_glm_grad_wide has no instantiation PTW = %d", g->PTW);
+    }
+}
+// k_glm_grad, or k_glm_grad_wide on a wide plan, at the positions q (strides sc,
+// sp: glm.h) of C chains, S slices
 static int launch_grad(const GlmPlan* g, const float* q, int sc, int sp, int64_t C, int S,
                        float* part, hipStream_t st) {
+    if (g->wide) {
+        switch (g->dev.family) {
+            case MC_GLM_NORMAL: return launch_wide_fam<MC_GLM_NORMAL>(g, q, sc, sp, C, S, part, st);
+            case MC_GLM_BERNOULLI_LOGIT:
+                return launch_wide_fam<MC_GLM_BERNOULLI_LOGIT>(g, q, sc, sp, C, S, part, st);
+            default: return launch_wide_fam<MC_GLM_POISSON_LOG>(g, q, sc, sp, C, S, part, st);
+        }
+    }
     switch (g->dev.family) {
         case MC_GLM_NORMAL: return launch_grad_fam<MC_GLM_NORMAL>(g, q, sc, sp, C, S, part, st);
         case MC_GLM_BERNOULLI_LOGIT:

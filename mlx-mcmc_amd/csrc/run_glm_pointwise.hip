@@ -19,6 +19,11 @@ int64_t glm_pw_elements(const mc_program* p) { return p->glm->dev.N; }
 int glm_pw_enable(mc_program* p) {
     GlmPlan* g = p->glm;
     if (g->d_norm) return MC_OK;
+    if (g->wide)
+        return fail(MC_ERR_UNSUPPORTED,
+                    "pointwise: a program of mc_program_create_glm_wide (glm_kernel=\"wide\") has no "
+                    "pointwise view: k_glm_pointwise keeps its X^T operands in registers and takes "
+                    "at most %d columns on a program of mc_program_create_glm", MC_GLM_MAX_P);
     if (g->dev.n_priors > 0)
         return fail(MC_ERR_UNSUPPORTED,
                     "pointwise: this design-matrix program carries %d prior term%s; a "

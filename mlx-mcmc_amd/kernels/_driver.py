@@ -92,11 +92,13 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
                 progress_every: Optional[int] = None, return_trace: bool = False,
                 keep_on_device: bool = False, initial_positions=None, num_slices: int = 0,
                 slice_kernel: str = "auto", inverse_mass_matrix=None,
-                adapt_mass_matrix: bool = False, nuts_kernel: str = "auto"):
+                adapt_mass_matrix: bool = False, nuts_kernel: str = "auto",
+                glm_kernel: str = "auto"):
     import torch
 
     if algorithm not in ("hmc", "nuts"):
         raise ValueError(algorithm)
+    _trace.check_glm_kernel(glm_kernel)
     if num_samples < 0 or num_warmup < 0:
         raise ValueError("num_samples and num_warmup must be non-negative")
     k = _as_key(key)
@@ -131,7 +133,8 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
         glm = "a mass matrix"
     program = _trace.compile_model(log_prob_fn, initial_params, slices=num_slices,
                                    slice_kernel=slice_kernel, glm=glm,
-                                   require_glm="nuts_kernel='glm'" if nuts_glm else None)
+                                   require_glm="nuts_kernel='glm'" if nuts_glm else None,
+                                   glm_kernel=glm_kernel)
     if (algorithm == "nuts" and num_slices == 0 and slice_kernel == "auto" and not use_metric
             and not nuts_glm):
         # a large regression's affine terms as expression terms: the sliced
@@ -272,6 +275,7 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
         info.extra["kernel_note"] = note
     if program.model.glm is not None:
         info.extra["glm_slices"] = program.glm_slices(C)
+        info.extra["glm_kernel"] = program.glm_kernel
     if algorithm == "hmc" and not use_metric and program.hmc_dense:
         # (slices, slots) of the dense route: a chain pair per workgroup
         info.extra["hmc_dense"] = program.hmc_dense

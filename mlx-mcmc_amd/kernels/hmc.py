@@ -26,6 +26,11 @@ and ``adapt_mass_matrix=True`` adapts it per chain during warmup (Stan's
 windows, csrc/metric.h); either one runs the chain-per-workgroup kernel
 ``k_hmc``.  ``RunInfo.extra["inverse_mass_matrix"]`` holds the final [C, D]
 metric, which a second run can start from.
+``glm_kernel``: "auto" runs a design-matrix model (``X @ beta``) of up to 256
+columns on ``k_glm_grad`` (csrc/glm.h) and refuses a wider one; "wide" runs it on
+the column-split kernel ``k_glm_grad_wide`` (csrc/glm_wide.h: up to 1024 columns,
+a quarter of the gradient block's registers per lane), and raises ``ValueError``
+for a model that is not a design-matrix model.
 Vector-valued parameters are supported (the reference's ``float()`` store,
 hmc.py:192, rejects them — SURVEY Q6).
 """
@@ -38,7 +43,7 @@ def hmc(log_prob_fn, initial_params, num_samples=1000, num_warmup=1000, step_siz
         num_leapfrog_steps=10, adapt_step_size=True, target_accept=0.8, key=None, *,
         num_chains=1, chain_offset=0, progress=True, return_info=False, return_trace=False,
         keep_on_device=False, initial_positions=None, num_slices=0, slice_kernel="auto",
-        inverse_mass_matrix=None, adapt_mass_matrix=False):
+        inverse_mass_matrix=None, adapt_mass_matrix=False, glm_kernel="auto"):
     """Hamiltonian Monte Carlo sampler using gradient information.
 
     Returns ``(samples, acceptance_rate)`` like the reference: ``samples`` maps
@@ -54,7 +59,8 @@ def hmc(log_prob_fn, initial_params, num_samples=1000, num_warmup=1000, step_siz
         chain_offset=chain_offset, progress=progress, return_trace=return_trace,
         keep_on_device=keep_on_device, initial_positions=initial_positions,
         num_slices=num_slices, slice_kernel=slice_kernel,
-        inverse_mass_matrix=inverse_mass_matrix, adapt_mass_matrix=adapt_mass_matrix)
+        inverse_mass_matrix=inverse_mass_matrix, adapt_mass_matrix=adapt_mass_matrix,
+        glm_kernel=glm_kernel)
     if return_info:
         return samples, rate, info
     return samples, rate

@@ -26,6 +26,9 @@ or a mass matrix, raises ``ValueError``.  Without the option ``nuts()`` declines
 design-matrix models, as before.
 ``num_slices``: data slices per chain (0: the automatic plan, as ``hmc()``); with
 ``nuts_kernel="glm"`` row slices per chain block, as ``hmc()`` takes them.
+``glm_kernel``: with ``nuts_kernel="glm"``, "wide" takes the gradient launches to
+the column-split kernel ``k_glm_grad_wide`` (csrc/glm_wide.h: up to 1024 columns),
+as ``hmc()`` takes it; "auto" keeps ``k_glm_grad`` and its cap of 256.
 
 ``slice_mode="reference"`` (default) reproduces the reference's float32
 slice variable: u = f32 exp(log u) rounds to the smallest denormal (log u =
@@ -57,7 +60,7 @@ def nuts(log_prob_fn, initial_params, num_samples=1000, num_warmup=1000, step_si
          num_chains=1, chain_offset=0, slice_mode="reference", progress=True,
          return_info=False, return_trace=False, keep_on_device=False,
          initial_positions=None, nuts_kernel="auto", num_slices=0,
-         inverse_mass_matrix=None, adapt_mass_matrix=False):
+         inverse_mass_matrix=None, adapt_mass_matrix=False, glm_kernel="auto"):
     """No-U-Turn Sampler (NUTS) for efficient HMC sampling.
 
     Returns ``(samples, acceptance_rate)`` like the reference, where the rate
@@ -81,7 +84,7 @@ def nuts(log_prob_fn, initial_params, num_samples=1000, num_warmup=1000, step_si
         initial_positions=initial_positions,
         num_slices=1 if nuts_kernel == "tape" else int(num_slices),
         inverse_mass_matrix=inverse_mass_matrix, adapt_mass_matrix=adapt_mass_matrix,
-        nuts_kernel=nuts_kernel)
+        nuts_kernel=nuts_kernel, glm_kernel=glm_kernel)
     if return_info:
         return samples, rate, info
     return samples, rate
