@@ -1169,9 +1169,9 @@ int mc_debug_rank_path(int path);
  * The result is an ordinary mc_program for mc_state_bytes / _offsets / _init,
  * mc_logp_grad, mc_hmc_run / mc_hmc_workspace_bytes, mc_program_set_slices /
  * _num_slices / _kernel_note / _num_params / _destroy (mc_program_slice_kernel
- * returns 3) and the pointwise statistics below; every other entry point that
- * takes a program returns MC_ERR_UNSUPPORTED (or -1 / 0 where it returns a
- * count).
+ * returns 3), the pointwise statistics below and mc_glm_predictive; every other
+ * entry point that takes a program returns MC_ERR_UNSUPPORTED (or -1 / 0 where
+ * it returns a count).
  * Pointwise statistics (csrc/glm_pointwise.h).  On a program WITHOUT prior
  * terms (a likelihood passed alone; with priors: MC_ERR_UNSUPPORTED)
  * mc_program_enable_pointwise builds the GLM view — the Poisson family's
@@ -1185,7 +1185,8 @@ int mc_debug_rank_path(int path);
  * matrix receives [C, S, N]).  The draw blocks depend on (C, S, N) only: two
  * calls give the same bits, with or without the matrix.  The view is not the
  * term view of other programs: mc_psis_* and mc_predictive* return
- * MC_ERR_UNSUPPORTED for a design-matrix program.  num_slices here
+ * MC_ERR_UNSUPPORTED for a design-matrix program (its predictive replicates
+ * are mc_glm_predictive's, below).  num_slices here
  * is row slices per chain block: 0 automatic (enough that slices x chain
  * blocks cover the CUs, at most 64 and at most one 32-row tile per wave),
  * 1..64 that many.  A chain's draws are those of mc_hmc_run on the tape up to
@@ -1261,6 +1262,48 @@ int mc_nuts_run_glm(const mc_program* prog, const mc_run_config* cfg,
 /* Measurement hook: the ticks enqueued and host polls of mc_nuts_run_glm since
  * the last call (either pointer may be NULL); resets both.                    */
 int mc_debug_glm_nuts_stats(int64_t* ticks, int64_t* polls);
+
+/* Posterior predictive replicates of a design-matrix program over kept draws
+ * (csrc/glm_predictive.h): mc_predictive_eq's arguments, fields (MC_PP_*),
+ * thinning, offsets and workspace rule on a program of mc_program_create_glm
+ * WITHOUT prior terms (a likelihood passed alone; mc_program_enable_pointwise
+ * is not needed).  Over all C * S' processed draws (S' = ceil(S / thin);
+ * processed draw (c, k) is row c * S + k * thin of samples_dev) the linear
+ * predictor is one FP32 MFMA product that is never stored.
+ * Definition.  The replicate of (chain c, iteration s, observation o) is the
+ * existing sampler applied to the f32 eta the kernel forms as
+ * mc_pointwise_stats forms it — the products X[o, k] * beta[k] added k
+ * ascending, then + intercept, then + offset — on the counter mc_predictive
+ * uses, (seed, c + chain_offset, s + iter_offset, MC_RNG_TAG_PREDICT, sub, o):
+ *   MC_GLM_NORMAL           mc_predictive_draw(MC_DIST_NORMAL, eta, scale): the
+ *                           scale operand's constant, or its transform applied
+ *                           to the draw's parameter once per draw
+ *   MC_GLM_BERNOULLI_LOGIT  mc_predictive_draw_discrete(MC_DISCRETE_BERNOULLI, 0, eta)
+ *   MC_GLM_POISSON_LOG      mc_predictive_draw_discrete(MC_DISCRETE_POISSON, 0, eta)
+ * (the host functions remain the definition: no sampler is restated).  eta's
+ * bits do not depend on how the draws are split into blocks, so a replicate is
+ * a pure function of the counter and the draw's parameters: shards of chains
+ * (chain_offset), shards of iterations (iter_offset), thinned runs and runs with
+ * or without yrep reproduce the same bytes.  A NaN eta or a scale that is not
+ * > 0 gives NaN, counted in MC_PP_NONFINITE.  BELOW compares with y_o;
+ * equal_dev (NULL or [N] f64: the finite replicates equal to y_o) is taken for
+ * the two count families only (MC_ERR_UNSUPPORTED for the normal family);
+ * yrep_dev is NULL or [C][S'][N] f32.
+ * Errors, each before any device work: MC_ERR_UNSUPPORTED for a program that
+ * is not of mc_program_create_glm, for one with prior terms and for one of
+ * mc_program_create_glm_wide (the kernel keeps its X^T operands in registers:
+ * MC_GLM_MAX_P columns); MC_ERR_INVALID for C, S or thin < 1, a C * S that
+ * overflows, NULL samples_dev / stats_dev, chain or iteration ids beyond 32
+ * bits and a workspace below mc_glm_predictive_workspace_bytes(prog, C, S,
+ * thin) bytes (0 is possible; the draw blocks depend on (C, S, thin, N) only).
+ * mc_predictive* keep declining design-matrix programs.                       */
+int64_t mc_glm_predictive_workspace_bytes(const mc_program* prog, int64_t C, int64_t S,
+                                          int64_t thin);
+int mc_glm_predictive(const mc_program* prog, int64_t C, int64_t S, int64_t thin, uint64_t seed,
+                      int64_t chain_offset, int64_t iter_offset, const float* samples_dev,
+                      double* stats_dev /* [MC_PP_COUNT][N] */, double* equal_dev /* [N] or NULL */,
+                      float* yrep_dev /* [C][S'][N] or NULL */, void* workspace_dev,
+                      int64_t workspace_bytes, void* hip_stream);
 
 const char* mc_last_error(void);
 int32_t mc_abi_version(void);

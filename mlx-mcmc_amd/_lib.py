@@ -383,6 +383,11 @@ SIGNATURES = [
     ("mc_predictive_eq", ctypes.c_int,
      [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64,
       ctypes.c_int64, _VP, _VP, _VP, _VP, _VP, ctypes.c_int64, _VP]),
+    ("mc_glm_predictive_workspace_bytes", ctypes.c_int64,
+     [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    ("mc_glm_predictive", ctypes.c_int,
+     [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64,
+      ctypes.c_int64, _VP, _VP, _VP, _VP, _VP, ctypes.c_int64, _VP]),
     ("mc_psis_tail_len", ctypes.c_int64, [ctypes.c_int64, ctypes.c_double]),
     ("mc_psis_fit_host", ctypes.c_int,
      [_VP, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_double),

@@ -1989,7 +1989,9 @@ def refuse_glm(model: TracedModel, what: str) -> None:
                          "Metropolis-Hastings, the metric, PSIS-LOO and the posterior "
                          "predictive entry points do not take them yet (NUTS does when asked "
                          "to: nuts(..., nuts_kernel='glm') / MCMC.run(method='nuts', "
-                         "nuts_kernel='glm'))")
+                         "nuts_kernel='glm'); posterior predictive replicates of the "
+                         "likelihood alone do when asked to: posterior_predictive(..., "
+                         "predictive_kernel='glm'))")
 
 
 _GLM_POINTWISE_FORM = (
@@ -2031,20 +2033,31 @@ def compile_model(log_prob_fn, initial_params: dict, slices: int = 0,
     return prog
 
 
+def check_predictive_kernel(predictive_kernel: str) -> None:
+    if predictive_kernel not in ("auto", "glm"):
+        raise ValueError(f"predictive_kernel must be 'auto' or 'glm', not {predictive_kernel!r}")
+
+
 def pointwise_program(log_likelihood_fn, layout: ParamLayout,
-                      glm: Optional[str] = None) -> Program:
+                      glm: Optional[str] = None, require_glm: Optional[str] = None) -> Program:
     """A likelihood traced like ``log_prob`` over the parameters of ``layout``,
     its terms in trace order (every element one observation), with the
     pointwise view enabled (diagnostics.pointwise_log_likelihood).  A
     design-matrix likelihood (one ``mx.sum(Family(X @ beta ...).log_prob(y))``
     alone: N observations) gets the view of csrc/glm_pointwise.h, which serves
     the pointwise statistics only — glm: None where that is enough, else the
-    caller's name (LOO, predictive) for the ValueError that refuses it."""
+    caller's name (LOO, predictive) for the ValueError that refuses it.
+    require_glm: the caller's name where only a design-matrix likelihood runs
+    (posterior_predictive(predictive_kernel="glm")), for the ValueError that
+    refuses any other."""
     _lib.require_device()
     init = {n: np.zeros(shp, np.float32) for n, shp in zip(layout.names, layout.shapes)}
     model = trace(log_likelihood_fn, init, keep_order=True)
     if glm is not None:
         refuse_glm(model, glm)
+    if require_glm is not None and model.glm is None:
+        raise ValueError(f"{require_glm} takes a design-matrix likelihood only: "
+                         + _GLM_POINTWISE_FORM)
     if model.glm is not None and model.terms:
         raise ValueError(f"{len(model.terms)} term(s) beside the X @ beta likelihood: "
                          + _GLM_POINTWISE_FORM)

@@ -654,7 +654,8 @@ def merge_predictive(parts):
 
 
 def posterior_predictive(log_likelihood_fn, samples, layout=None, *, seed=0, thin=1,
-                         replicates=False, chain_offset=0, iter_offset=0, group=None):
+                         replicates=False, chain_offset=0, iter_offset=0, group=None,
+                         predictive_kernel="auto"):
     """Posterior predictive replicates and per-observation checks over the
     kept draws, on the device.
 
@@ -688,34 +689,56 @@ def posterior_predictive(log_likelihood_fn, samples, layout=None, *, seed=0, thi
     ``replicates``, the [C, S', M] float32 device tensor (small problems only).
     With an initialised process group (``group=False`` stays local) the ranks'
     partials are gathered and merged in rank order; the replicates stay this
-    rank's."""
+    rank's.
+
+    ``predictive_kernel="glm"`` takes a design-matrix likelihood instead —
+    exactly one ``mx.sum(Family(X @ beta ...).log_prob(y))`` of the Normal,
+    Bernoulli (logits) or Poisson (log_rate) family, passed alone, at most 256
+    columns — on the MFMA kernel of csrc/glm_predictive.h (mc_glm_predictive):
+    the replicate of an entry is the same sampler applied to the f32 ``eta``
+    the pointwise kernel forms, on the same counter, so everything above holds
+    and the result has the same keys (``equal`` and ``pit_mid`` for the two
+    count families).  ``X`` may be any covariates: replicates at ``X_new`` are
+    predictive draws there (``below`` and ``pit`` then refer to the ``y``
+    passed with it).  Any other likelihood is a ``ValueError``; the default
+    ``"auto"`` keeps refusing design-matrix likelihoods."""
     import torch
 
     from . import _trace
 
+    _trace.check_predictive_kernel(predictive_kernel)
     thin = int(thin)
     if thin < 1:
         raise ValueError("thin must be >= 1")
     x, lay = _pointwise_inputs(samples, layout)
     C, S, D = x.shape
-    prog = _trace.pointwise_program(log_likelihood_fn, lay,
-                                    glm="posterior predictive replicates "
-                                        "(diagnostics.posterior_predictive)")
+    glm = predictive_kernel == "glm"
+    if glm:
+        prog = _trace.pointwise_program(log_likelihood_fn, lay,
+                                        require_glm="predictive_kernel='glm'")
+    else:
+        prog = _trace.pointwise_program(log_likelihood_fn, lay,
+                                        glm="posterior predictive replicates "
+                                            "(diagnostics.posterior_predictive)")
     lib = _lib.load()
     M = prog.num_elements
-    nb = lib.mc_predictive_workspace_bytes(prog.handle, C, S, thin)
+    size = lib.mc_glm_predictive_workspace_bytes if glm else lib.mc_predictive_workspace_bytes
+    nb = size(prog.handle, C, S, thin)
     if nb < 0:   # (an unsupported term is reported here: nothing is launched)
         _lib.check(int(nb))
     Sp = (S + thin - 1) // thin
     st = torch.empty((_lib.MC_PP_COUNT, M), dtype=torch.float64, device=x.device)
-    eq = (torch.empty(M, dtype=torch.float64, device=x.device)
-          if lib.mc_program_num_count_terms(prog.handle) > 0 else None)
+    if glm:
+        ties = prog.model.glm.family != _lib.MC_GLM_NORMAL
+    else:
+        ties = lib.mc_program_num_count_terms(prog.handle) > 0
+    eq = torch.empty(M, dtype=torch.float64, device=x.device) if ties else None
     rep = torch.empty((C, Sp, M), dtype=torch.float32, device=x.device) if replicates else None
     ws = torch.empty(max(int(nb), 1), dtype=torch.uint8, device=x.device)
-    _lib.check(lib.mc_predictive_eq(prog.handle, C, S, thin, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                    int(chain_offset), int(iter_offset), _lib.ptr(x),
-                                    _lib.ptr(st), _lib.ptr(eq), _lib.ptr(rep), _lib.ptr(ws), nb,
-                                    _lib.stream_handle()))
+    run = lib.mc_glm_predictive if glm else lib.mc_predictive_eq
+    _lib.check(run(prog.handle, C, S, thin, int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_offset),
+                   int(iter_offset), _lib.ptr(x), _lib.ptr(st), _lib.ptr(eq), _lib.ptr(rep),
+                   _lib.ptr(ws), nb, _lib.stream_handle()))
     host = st.cpu().numpy()   # (synchronises: prog, x and ws outlive the launch)
     part = {f: host[k].copy() for k, f in enumerate(PP_FIELDS)}
     if eq is not None:

@@ -175,17 +175,19 @@ class MCMC:
         samples, layout = self._kept_draws()
         return _diag.loo(log_likelihood_fn, samples, layout, r_eff=r_eff, group=False)
 
-    def posterior_predictive(self, log_likelihood_fn, seed=None, thin=1, replicates=False):
+    def posterior_predictive(self, log_likelihood_fn, seed=None, thin=1, replicates=False,
+                             predictive_kernel="auto"):
         """Posterior predictive replicates of ``log_likelihood_fn``'s observations
         over the kept draws, reduced on the device to per-observation mean,
         variance and PIT (diagnostics.posterior_predictive).  ``seed`` defaults
         to the run's ``random_seed``; chains are numbered from the run's
-        ``chain_offset``."""
+        ``chain_offset``.  ``predictive_kernel="glm"``: a design-matrix
+        likelihood (``X @ beta``), on the MFMA kernel."""
         samples, layout = self._kept_draws()
         return _diag.posterior_predictive(
             log_likelihood_fn, samples, layout,
             seed=self._random_seed if seed is None else seed, thin=thin, replicates=replicates,
-            chain_offset=self._chain_offset, group=False)
+            chain_offset=self._chain_offset, group=False, predictive_kernel=predictive_kernel)
 
     def print_summary(self, credible_interval=0.95):
         summary = self.summary(credible_interval)
