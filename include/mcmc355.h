@@ -1169,7 +1169,8 @@ int mc_debug_rank_path(int path);
  * The result is an ordinary mc_program for mc_state_bytes / _offsets / _init,
  * mc_logp_grad, mc_hmc_run / mc_hmc_workspace_bytes, mc_program_set_slices /
  * _num_slices / _kernel_note / _num_params / _destroy (mc_program_slice_kernel
- * returns 3), the pointwise statistics below and mc_glm_predictive; every other
+ * returns 3), the pointwise statistics below, mc_glm_predictive and
+ * mc_glm_psis_loo; every other
  * entry point that takes a program returns MC_ERR_UNSUPPORTED (or -1 / 0 where
  * it returns a count).
  * Pointwise statistics (csrc/glm_pointwise.h).  On a program WITHOUT prior
@@ -1186,7 +1187,7 @@ int mc_debug_rank_path(int path);
  * calls give the same bits, with or without the matrix.  The view is not the
  * term view of other programs: mc_psis_* and mc_predictive* return
  * MC_ERR_UNSUPPORTED for a design-matrix program (its predictive replicates
- * are mc_glm_predictive's, below).  num_slices here
+ * are mc_glm_predictive's and its PSIS-LOO mc_glm_psis_loo's, below).  num_slices here
  * is row slices per chain block: 0 automatic (enough that slices x chain
  * blocks cover the CUs, at most 64 and at most one 32-row tile per wave),
  * 1..64 that many.  A chain's draws are those of mc_hmc_run on the tape up to
@@ -1304,6 +1305,40 @@ int mc_glm_predictive(const mc_program* prog, int64_t C, int64_t S, int64_t thin
                       double* stats_dev /* [MC_PP_COUNT][N] */, double* equal_dev /* [N] or NULL */,
                       float* yrep_dev /* [C][S'][N] or NULL */, void* workspace_dev,
                       int64_t workspace_bytes, void* hip_stream);
+
+/* PSIS-LOO of a design-matrix program over kept draws (csrc/glm_psis.h):
+ * mc_psis_loo's arguments, fields (MC_PSIS_*), tail layout and workspace rule
+ * on a program of mc_program_create_glm WITHOUT prior terms whose pointwise
+ * view is enabled (mc_program_enable_pointwise: the Poisson normaliser); M = N,
+ * one observation per row of X.  The definition "PSIS-LOO over kept draws"
+ * above, steps 1-8, holds verbatim, with l_s the f32 value mc_pointwise_stats
+ * forms on this program (the bits of its matrix; -0 taken as +0).  The
+ * C * S * N matrix is never stored: each of the eight select passes and the
+ * gather re-forms it as one FP32 MFMA product, nine in all; the pick between
+ * passes and the fit are mc_psis_loo's kernels.  The draw blocks depend on
+ * (C, S, N) only, counts are integers and every f64 sum has a fixed order: two
+ * calls give the same bits, with or without tail_dev.  No atomics, nothing
+ * waits on another workgroup.
+ * Errors, each before any device work: MC_ERR_UNSUPPORTED for a program that is
+ * not of mc_program_create_glm, for one of mc_program_create_glm_wide (the
+ * kernels keep their X^T operands in registers: MC_GLM_MAX_P columns), for one
+ * with prior terms, for C * S beyond the 32-bit draw counters, for a tail above
+ * 2048 (kPsisMaxTail) and for N > INT32_MAX; MC_ERR_INVALID for a program whose
+ * pointwise view was not enabled, C or S < 1, an r_eff that is not positive and
+ * finite, NULL samples_dev / out_dev and a workspace that is NULL, below
+ * mc_glm_psis_workspace_bytes(prog, C, S, r_eff) bytes or not 8-byte aligned.
+ * mc_psis_* keep declining design-matrix programs.                            */
+int64_t mc_glm_psis_workspace_bytes(const mc_program* prog, int64_t C, int64_t S, double r_eff);
+int mc_glm_psis_loo(const mc_program* prog, int64_t C, int64_t S, double r_eff,
+                    const float* samples_dev, double* out_dev /* [MC_PSIS_COUNT][N] */,
+                    float* tail_dev /* [N][Mt] or NULL */, void* workspace_dev,
+                    int64_t workspace_bytes, void* hip_stream);
+/* Measurement hook: one mc_glm_psis_loo without tail_dev, with an event after
+ * every stage; SYNCHRONISES on the last.  ms[18] receives the milliseconds of
+ * count and pick of the eight select passes alternating, the gather, the fit. */
+int mc_debug_glm_psis_times(const mc_program* prog, int64_t C, int64_t S, double r_eff,
+                            const float* samples_dev, double* out_dev, void* workspace_dev,
+                            int64_t workspace_bytes, void* hip_stream, float* ms);
 
 const char* mc_last_error(void);
 int32_t mc_abi_version(void);

@@ -397,6 +397,14 @@ SIGNATURES = [
     ("mc_psis_loo", ctypes.c_int,
      [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _VP, _VP, _VP, _VP, ctypes.c_int64,
       _VP]),
+    ("mc_glm_psis_workspace_bytes", ctypes.c_int64,
+     [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_double]),
+    ("mc_glm_psis_loo", ctypes.c_int,
+     [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _VP, _VP, _VP, _VP, ctypes.c_int64,
+      _VP]),
+    ("mc_debug_glm_psis_times", ctypes.c_int,
+     [_VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _VP, _VP, _VP, ctypes.c_int64, _VP,
+      ctypes.POINTER(ctypes.c_float)]),
     ("mc_rank_diag_workspace_bytes", ctypes.c_int64,
      [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
     ("mc_rank_diag", ctypes.c_int,

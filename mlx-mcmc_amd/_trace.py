@@ -1991,7 +1991,8 @@ def refuse_glm(model: TracedModel, what: str) -> None:
                          "to: nuts(..., nuts_kernel='glm') / MCMC.run(method='nuts', "
                          "nuts_kernel='glm'); posterior predictive replicates of the "
                          "likelihood alone do when asked to: posterior_predictive(..., "
-                         "predictive_kernel='glm'))")
+                         "predictive_kernel='glm'); PSIS-LOO of the likelihood alone does "
+                         "when asked to: loo(..., loo_kernel='glm'))")
 
 
 _GLM_POINTWISE_FORM = (
@@ -2038,6 +2039,11 @@ def check_predictive_kernel(predictive_kernel: str) -> None:
         raise ValueError(f"predictive_kernel must be 'auto' or 'glm', not {predictive_kernel!r}")
 
 
+def check_loo_kernel(loo_kernel: str) -> None:
+    if loo_kernel not in ("auto", "glm"):
+        raise ValueError(f"loo_kernel must be 'auto' or 'glm', not {loo_kernel!r}")
+
+
 def pointwise_program(log_likelihood_fn, layout: ParamLayout,
                       glm: Optional[str] = None, require_glm: Optional[str] = None) -> Program:
     """A likelihood traced like ``log_prob`` over the parameters of ``layout``,
@@ -2050,7 +2056,6 @@ def pointwise_program(log_likelihood_fn, layout: ParamLayout,
     require_glm: the caller's name where only a design-matrix likelihood runs
     (posterior_predictive(predictive_kernel="glm")), for the ValueError that
     refuses any other."""
-    _lib.require_device()
     init = {n: np.zeros(shp, np.float32) for n, shp in zip(layout.names, layout.shapes)}
     model = trace(log_likelihood_fn, init, keep_order=True)
     if glm is not None:
@@ -2061,6 +2066,7 @@ def pointwise_program(log_likelihood_fn, layout: ParamLayout,
     if model.glm is not None and model.terms:
         raise ValueError(f"{len(model.terms)} term(s) beside the X @ beta likelihood: "
                          + _GLM_POINTWISE_FORM)
+    _lib.require_device()
     prog = Program(model)
     prog.enable_pointwise()
     return prog

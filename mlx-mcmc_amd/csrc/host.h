@@ -205,9 +205,10 @@ void pw_free(mc_program* p);  // (run_pointwise.hip)
 
 // ---- design-matrix programs (include/mcmc355.h mc_glm) ---------------------------
 // They run mc_logp_grad, mc_state_init and mc_hmc_run on the MFMA kernels of
-// glm.h, mc_pointwise_stats on that of glm_pointwise.h and mc_glm_predictive
-// (run_glm_predictive.hip) on that of glm_predictive.h; every other entry
-// point that takes a program declines them by name.
+// glm.h, mc_pointwise_stats on that of glm_pointwise.h, mc_glm_predictive
+// (run_glm_predictive.hip) on that of glm_predictive.h and mc_glm_psis_loo
+// (run_glm_psis.hip) on those of glm_psis.h; every other entry point that
+// takes a program declines them by name.
 inline bool is_glm(const mc_program* p) { return p && p->glm != nullptr; }
 #define MC_GLM_REFUSE(p, what)                                                              \
     do {                                                                                    \

@@ -175,6 +175,29 @@ struct PsisWs {
     float* tail;      // [M, Mt] as gathered (unsorted)
 };
 
+// The workspace's arrays in order (f64 first; every size a multiple of 4
+// bytes): its size in bytes, and the pointers into ws when W is given.
+inline int64_t psis_carve(int64_t M, int64_t B, int64_t Mt, void* ws, PsisWs* W) {
+    char* p = (char*)ws;
+    int64_t at = 0;
+    auto take = [&](int64_t bytes) {
+        char* r = p ? p + at : nullptr;
+        at += bytes;
+        return r;
+    };
+    PsisWs w;
+    w.rest = (double*)take(B * M * 8);
+    w.cnt = (uint32_t*)take(B * kPsisSlots * M * 4);
+    w.off = (uint32_t*)take(B * M * 4);
+    w.nf = (uint32_t*)take(B * M * 4);
+    w.lo = (uint32_t*)take(M * 4);
+    w.kmin = (uint32_t*)take(M * 4);
+    w.ntail = (uint32_t*)take(M * 4);
+    w.tail = (float*)take(M * (Mt > 1 ? Mt : 1) * 4);
+    if (W) *W = w;
+    return at;
+}
+
 template <int NMAX, bool LG>
 __global__ __launch_bounds__(kPwBlock) void k_psis_count(PwCtx P, int64_t N, int64_t per,
                                                          const float* __restrict__ samples,

@@ -15,9 +15,8 @@ struct PsisPlan {
 int psis_plan(const mc_program* p, int64_t C, int64_t S, double r_eff, PsisPlan* out) {
     if (!p) return fail(MC_ERR_INVALID, "program is NULL");
     if (is_glm(p))
-        return fail(MC_ERR_UNSUPPORTED, "psis: a design-matrix (X @ beta) program has pointwise "
-                    "statistics (mc_pointwise_stats) only: the PSIS kernels read a term view "
-                    "(PwCtx) such a program does not have");
+        return fail(MC_ERR_UNSUPPORTED, "psis: the PSIS kernels here read a term view (PwCtx) a "
+                    "design-matrix (X @ beta) program does not have; mc_glm_psis_loo takes it");
     const PwView* v = (const PwView*)p->pw;
     if (!v) return fail(MC_ERR_INVALID, "psis: call mc_program_enable_pointwise first");
     if (C < 1 || S < 1) return fail(MC_ERR_INVALID, "psis: C and S must be >= 1");
@@ -40,27 +39,8 @@ int psis_plan(const mc_program* p, int64_t C, int64_t S, double r_eff, PsisPlan*
     return MC_OK;
 }
 
-// The workspace's arrays in order (f64 first; every size a multiple of 4 bytes).
 int64_t psis_carve(const PsisPlan& L, void* ws, mc::PsisWs* W) {
-    const int64_t M = L.v->M, B = L.B;
-    char* p = (char*)ws;
-    int64_t at = 0;
-    auto take = [&](int64_t bytes) {
-        char* r = p ? p + at : nullptr;
-        at += bytes;
-        return r;
-    };
-    mc::PsisWs w;
-    w.rest = (double*)take(B * M * 8);
-    w.cnt = (uint32_t*)take(B * mc::kPsisSlots * M * 4);
-    w.off = (uint32_t*)take(B * M * 4);
-    w.nf = (uint32_t*)take(B * M * 4);
-    w.lo = (uint32_t*)take(M * 4);
-    w.kmin = (uint32_t*)take(M * 4);
-    w.ntail = (uint32_t*)take(M * 4);
-    w.tail = (float*)take(M * std::max<int64_t>(L.Mt, 1) * 4);
-    if (W) *W = w;
-    return at;
+    return mc::psis_carve(L.v->M, L.B, L.Mt, ws, W);
 }
 
 }  // namespace

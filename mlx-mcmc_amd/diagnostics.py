@@ -384,16 +384,23 @@ def _pointwise_inputs(samples, layout):
     or [S, *shape] for one chain.  Without a layout the parameter shapes are
     what follows the leading axes: one chain when some array is 1-D, else
     [C, S, ...] (pass the run's layout for one chain of vector parameters)."""
+    draws, lay = _pointwise_host_inputs(samples, layout)
+    x = _as_device(draws)
+    if x.shape[2] != lay.size:
+        raise ValueError(f"samples have {x.shape[2]} elements per draw, the layout "
+                         f"{lay.size}")
+    return x, lay
+
+
+def _pointwise_host_inputs(samples, layout):
+    """_pointwise_inputs before the device is asked for: (the buffer as passed,
+    or the dict's arrays as one host [C, S, D] array; the layout)."""
     from . import _trace
 
     if not isinstance(samples, dict):
         if layout is None:
             raise ValueError("a [C, S, D] buffer needs its layout")
-        x = _as_device(samples)
-        if x.shape[2] != layout.size:
-            raise ValueError(f"samples have {x.shape[2]} elements per draw, the layout "
-                             f"{layout.size}")
-        return x, layout
+        return samples, layout
     arrs = {k: np.asarray(_trace._to_numpy(v), np.float32) for k, v in samples.items()}
     if not arrs:
         raise ValueError("samples is empty")
@@ -419,7 +426,7 @@ def _pointwise_inputs(samples, layout):
     lay = _trace.layout_of({n: np.zeros(arrs[n].shape[lead:], np.float32) for n in names})
     if layout is not None and list(lay.shapes) != [tuple(s) for s in layout.shapes]:
         raise ValueError("samples do not match the layout's parameter shapes")
-    return _as_device(np.concatenate(cols, axis=2)), lay
+    return np.concatenate(cols, axis=2), lay
 
 
 def _pointwise_launch(prog, x, matrix=False):
@@ -525,7 +532,8 @@ def _refuse_sharded_draws(group, why=None):
                          "group=False for this rank's draws alone")
 
 
-def loo(log_likelihood_fn, samples, layout=None, *, r_eff=1.0, tail=False, group=None) -> dict:
+def loo(log_likelihood_fn, samples, layout=None, *, r_eff=1.0, tail=False, group=None,
+        loo_kernel="auto") -> dict:
     """PSIS-LOO (Vehtari, Gelman and Gabry 2017) of a likelihood over the kept
     draws, on the device (``pointwise_log_likelihood``'s arguments;
     mc_psis_loo, csrc/psis.h; the definition is stated in include/mcmc355.h).
@@ -550,30 +558,49 @@ def loo(log_likelihood_fn, samples, layout=None, *, r_eff=1.0, tail=False, group
 
     PSIS is not mergeable over shards of draws: with an initialised process
     group of more than one rank this raises ``ValueError`` unless
-    ``group=False`` (this rank's draws alone)."""
+    ``group=False`` (this rank's draws alone).
+
+    ``loo_kernel="glm"`` takes a design-matrix likelihood instead — exactly one
+    ``mx.sum(Family(X @ beta ...).log_prob(y))`` of the Normal, Bernoulli
+    (logits) or Poisson (log_rate) family, passed alone, at most 256 columns —
+    on the MFMA select and gather kernels of csrc/glm_psis.h
+    (mc_glm_psis_loo): the same definition on the values
+    ``pointwise_log_likelihood`` forms for such a likelihood, re-formed per
+    pass as one matrix product, and the same result keys.  Any other
+    likelihood is a ``ValueError``; the default ``"auto"`` keeps refusing
+    design-matrix likelihoods."""
     import torch
 
     from . import _trace
 
+    _trace.check_loo_kernel(loo_kernel)
     _refuse_sharded_draws(group)
     r_eff = float(r_eff)
     if not (r_eff > 0.0 and np.isfinite(r_eff)):
         raise ValueError("r_eff must be a positive finite scalar")
-    x, lay = _pointwise_inputs(samples, layout)
+    # (the likelihood is traced, and refused, before the device is asked for)
+    draws, lay = _pointwise_host_inputs(samples, layout)
+    glm = loo_kernel == "glm"
+    if glm:
+        prog = _trace.pointwise_program(log_likelihood_fn, lay, require_glm="loo_kernel='glm'")
+    else:
+        prog = _trace.pointwise_program(log_likelihood_fn, lay, glm="PSIS-LOO (diagnostics.loo)")
+    x, lay = _pointwise_inputs(draws, lay)
     C, S, D = x.shape
-    prog = _trace.pointwise_program(log_likelihood_fn, lay, glm="PSIS-LOO (diagnostics.loo)")
     stats, _ = _pointwise_launch(prog, x)
     lib = _lib.load()
     M = prog.num_elements
-    nb = lib.mc_psis_workspace_bytes(prog.handle, C, S, r_eff)
+    size = lib.mc_glm_psis_workspace_bytes if glm else lib.mc_psis_workspace_bytes
+    nb = size(prog.handle, C, S, r_eff)
     if nb < 0:   # (a tail beyond the kernel's capacity is reported here: nothing is launched)
         _lib.check(int(nb))
     mt = int(lib.mc_psis_tail_len(C * S, r_eff))
     out = torch.empty((_lib.MC_PSIS_COUNT, M), dtype=torch.float64, device=x.device)
     tl = torch.empty((M, mt), dtype=torch.float32, device=x.device) if tail else None
     ws = torch.empty(max(int(nb), 8), dtype=torch.uint8, device=x.device)
-    _lib.check(lib.mc_psis_loo(prog.handle, C, S, r_eff, _lib.ptr(x), _lib.ptr(out),
-                               _lib.ptr(tl), _lib.ptr(ws), nb, _lib.stream_handle()))
+    run = lib.mc_glm_psis_loo if glm else lib.mc_psis_loo
+    _lib.check(run(prog.handle, C, S, r_eff, _lib.ptr(x), _lib.ptr(out), _lib.ptr(tl),
+                   _lib.ptr(ws), nb, _lib.stream_handle()))
     host = out.cpu().numpy()   # (synchronises: prog, x and ws outlive the launch)
     with np.errstate(all="ignore"):
         lppd_i = np.log(stats["sumexp"]) + stats["max"] - np.log(stats["n"])

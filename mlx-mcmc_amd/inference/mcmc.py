@@ -169,11 +169,14 @@ class MCMC:
         samples, layout = self._kept_draws()
         return _diag.waic(log_likelihood_fn, samples, layout, group=False)
 
-    def loo(self, log_likelihood_fn, r_eff=1.0):
+    def loo(self, log_likelihood_fn, r_eff=1.0, loo_kernel="auto"):
         """PSIS-LOO of ``log_likelihood_fn`` over the kept draws, with the
-        per-observation Pareto khat diagnostic (diagnostics.loo)."""
+        per-observation Pareto khat diagnostic (diagnostics.loo).
+        ``loo_kernel="glm"``: a design-matrix likelihood (``X @ beta``), on the
+        MFMA select and gather kernels."""
         samples, layout = self._kept_draws()
-        return _diag.loo(log_likelihood_fn, samples, layout, r_eff=r_eff, group=False)
+        return _diag.loo(log_likelihood_fn, samples, layout, r_eff=r_eff, group=False,
+                         loo_kernel=loo_kernel)
 
     def posterior_predictive(self, log_likelihood_fn, seed=None, thin=1, replicates=False,
                              predictive_kernel="auto"):
