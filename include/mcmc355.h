@@ -1236,6 +1236,48 @@ int mc_program_create_glm_wide(const mc_glm* glm, const mc_term* priors, int32_t
                                int32_t n_params, float lp_const,
                                const float* data, int64_t n_data, mc_program** out);
 
+/* Softmax (multinomial-logit) regression on a design matrix
+ * (csrc/glm_softmax.h):  sum_i log softmax(eta_i)[y_i] + priors  with the K
+ * class logits of observation i
+ *     eta[i, k] = sum_p X[i, p] B[p, k]  [+ a[k]]
+ * All K columns of B are free (identifiability is the priors' business).
+ *   beta_offset  B[p, k] is parameter q[beta_offset + p * k_classes + k]: a
+ *                row-major [P, K] parameter
+ *   icpt_offset  the K class intercepts q[icpt_offset .. icpt_offset + K), or
+ *                a negative value for none
+ *   n, p, k      rows and columns of X, and the number of classes
+ *   x_pool       data pool offset of X (row-major, n * p)
+ *   y_pool       data pool offset of the labels (n): integers 0 .. k - 1 as
+ *                floats; any other value is MC_ERR_INVALID (the kernel has no
+ *                invalid-label path)
+ * The prior terms are those of mc_program_create_glm.  The (chain, class)
+ * pairs are the N dimension of mc_program_create_glm's two MFMA products: a
+ * gradient block of 32 columns holds 32 / Kp chains times Kp classes, Kp = k
+ * rounded up to a power of two, and the softmax runs across lanes of the
+ * accumulator.  Limits, each MC_ERR_UNSUPPORTED before any device work: 2 <= k
+ * <= MC_GLM_SOFTMAX_MAX_K, 1 <= p <= MC_GLM_MAX_P (whatever k is), n >= 1, the
+ * padded n * p below 2^31.  The result (family MC_GLM_CATEGORICAL_LOGIT) is a
+ * design-matrix program for mc_state_bytes / _offsets / _init, mc_logp_grad,
+ * mc_hmc_run / mc_hmc_workspace_bytes, mc_program_set_slices / _num_slices /
+ * _glm_slices / _kernel_note / _num_params / _destroy, with the guarantees of
+ * mc_program_create_glm (a chain's draws do not depend on the split of the
+ * chains; two calls give the same bits).  mc_nuts_run_glm,
+ * mc_program_enable_pointwise, mc_glm_predictive and mc_glm_psis_loo return
+ * MC_ERR_UNSUPPORTED for it, as every entry that refuses a design-matrix
+ * program does.                                                              */
+#define MC_GLM_CATEGORICAL_LOGIT 3
+#define MC_GLM_SOFTMAX_MAX_K     32
+typedef struct mc_glm_softmax {
+    int32_t beta_offset;   /* parameter offset of B[0, 0]                    */
+    int32_t icpt_offset;   /* parameter offset of a[0], or < 0: none         */
+    int64_t n, p, k;       /* rows and columns of X; classes                 */
+    int64_t x_pool;        /* data pool offset of X (row-major, n * p)       */
+    int64_t y_pool;        /* data pool offset of the labels (n)             */
+} mc_glm_softmax;
+int mc_program_create_glm_softmax(const mc_glm_softmax* glm, const mc_term* priors,
+                                  int32_t n_priors, int32_t n_params, float lp_const,
+                                  const float* data, int64_t n_data, mc_program** out);
+
 /* NUTS of a design-matrix program (csrc/glm_nuts.h): mc_nuts_run's config,
  * state, samples, trace and draw addressing, on mc_nuts_glm_workspace_bytes
  * bytes of device memory (-1 for any other program or a max_tree_depth outside

@@ -151,6 +151,8 @@ class McExpr(ctypes.Structure):
 MC_GLM_NORMAL, MC_GLM_BERNOULLI_LOGIT, MC_GLM_POISSON_LOG = range(3)
 MC_GLM_MAX_P = 256
 MC_GLM_WIDE_MAX_P = 1024  # mc_program_create_glm_wide (csrc/glm_wide.h)
+MC_GLM_CATEGORICAL_LOGIT = 3  # mc_program_create_glm_softmax (csrc/glm_softmax.h)
+MC_GLM_SOFTMAX_MAX_K = 32
 
 
 class McGlm(ctypes.Structure):
@@ -165,6 +167,20 @@ class McGlm(ctypes.Structure):
         ("offset_pool", ctypes.c_int64),
         ("intercept", McOperand),
         ("scale", McOperand),
+    ]
+
+
+class McGlmSoftmax(ctypes.Structure):
+    """mc_glm_softmax: eta[i, k] = X[i] . B[:, k] [+ a[k]] under a categorical-logit
+    likelihood of the labels."""
+    _fields_ = [
+        ("beta_offset", ctypes.c_int32),
+        ("icpt_offset", ctypes.c_int32),
+        ("n", ctypes.c_int64),
+        ("p", ctypes.c_int64),
+        ("k", ctypes.c_int64),
+        ("x_pool", ctypes.c_int64),
+        ("y_pool", ctypes.c_int64),
     ]
 
 
@@ -249,6 +265,9 @@ SIGNATURES = [
       ctypes.c_float, _VP, ctypes.c_int64, ctypes.POINTER(_VP)]),
     ("mc_program_create_glm_wide", ctypes.c_int,
      [ctypes.POINTER(McGlm), ctypes.POINTER(McTerm), ctypes.c_int32, ctypes.c_int32,
+      ctypes.c_float, _VP, ctypes.c_int64, ctypes.POINTER(_VP)]),
+    ("mc_program_create_glm_softmax", ctypes.c_int,
+     [ctypes.POINTER(McGlmSoftmax), ctypes.POINTER(McTerm), ctypes.c_int32, ctypes.c_int32,
       ctypes.c_float, _VP, ctypes.c_int64, ctypes.POINTER(_VP)]),
     ("mc_program_glm_slices", ctypes.c_int32, [_VP, ctypes.c_int64]),
     ("mc_program_glm_chain_block", ctypes.c_int32, [_VP]),

@@ -75,7 +75,7 @@ from __future__ import annotations
 import ctypes
 import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 
@@ -178,7 +178,8 @@ class Param:
         if self.view is not None:
             base, length = self.view[1], self.view[2]
         if len(self.base_shape) > 1 and self.view is None:
-            raise TraceError("indexing multi-dimensional parameters is not supported")
+            raise TraceError("indexing multi-dimensional parameters is not supported (a matrix "
+                             "parameter is used whole: " + _SOFTMAX_FORM + ")")
         if isinstance(idx, (int, np.integer)):
             i = int(idx)
             if i < 0:
@@ -229,14 +230,14 @@ class Param:
         return _affine_or_expr(lambda: Affine.product(other, self), _lib.MC_EX_MUL, other, self)
 
     def __add__(self, other):
-        if isinstance(other, (LogProbExpr, MatVec)):
+        if isinstance(other, (LogProbExpr, MatVec, MatMat)):
             return other + self
         if isinstance(other, Expr):
             return Expr.binary(_lib.MC_EX_ADD, self, other)
         return _affine_or_expr(lambda: Affine.lift(self) + other, _lib.MC_EX_ADD, self, other)
 
     def __radd__(self, other):
-        if isinstance(other, (LogProbExpr, MatVec)):
+        if isinstance(other, (LogProbExpr, MatVec, MatMat)):
             return other + self
         if isinstance(other, Expr):
             return Expr.binary(_lib.MC_EX_ADD, other, self)
@@ -299,6 +300,13 @@ GLM_DIST = 100  # Term.dist of the design-matrix likelihood (Python side only)
 GLM_FAMILIES = {"Normal": _lib.MC_GLM_NORMAL, "Bernoulli": _lib.MC_GLM_BERNOULLI_LOGIT,
                 "Poisson": _lib.MC_GLM_POISSON_LOG}
 
+_SOFTMAX_FORM = (
+    "softmax regression on a design matrix is mx.sum(Categorical(logits=X @ B [+ a])"
+    ".log_prob(y)): X a 2-D float data array [N, P] with P <= 256, B a whole, untransformed 2-D "
+    "parameter [P, K] with 2 <= K <= 32 classes, a (optional) a whole, untransformed 1-D "
+    "parameter of K class intercepts, y data of N integer labels in 0 .. K-1, beside Normal / "
+    "HalfNormal / Exponential / Gamma / Beta priors with constant arguments on the parameters")
+
 
 class MatVec:
     """A traced linear predictor X @ beta [+ constant] [+ intercept] [+ offset]
@@ -322,6 +330,11 @@ class MatVec:
         arr = np.asarray(_to_numpy(X))
         if arr.dtype == object or arr.dtype.kind not in "fiu" or arr.ndim != 2:
             raise TraceError(f"X @ beta with X of shape {arr.shape}: " + _GLM_FORM)
+        if len(beta.base_shape) == 2 and beta.view is None and not beta.xf:
+            return MatMat.of(arr, beta)
+        if len(beta.base_shape) == 2:
+            raise TraceError(f"X @ B with B = {beta!r} (a sliced, gathered or transformed "
+                             "matrix parameter): " + _SOFTMAX_FORM)
         if beta.xf or len(beta.base_shape) != 1 or (beta.view is not None
                                                     and beta.view[0] != "slice"):
             raise TraceError(f"X @ beta with beta = {beta!r} (a multi-dimensional, gathered, "
@@ -372,14 +385,76 @@ class MatVec:
         return f"MatVec(X{list(self.X.shape)} @ params[{self.beta[0]}:+{self.beta[1]}])"
 
 
+class MatMat:
+    """The traced class logits X @ B [+ a] of a softmax regression
+    (include/mcmc355.h mc_glm_softmax): B a whole 2-D parameter [P, K], a a whole
+    1-D parameter of K class intercepts.  Only `+ a` extends it and only
+    Categorical(logits=...) consumes it; the GLM families refuse it as a
+    multi-dimensional beta."""
+
+    __array_priority__ = 1000
+
+    def __init__(self, X, B, icpt=None):
+        self.X = X        # float32 [N, P]
+        self.B = B        # (parameter offset of B[0, 0], P, K)
+        self.icpt = icpt  # parameter offset of a[0], or None
+        self.shape = (X.shape[0], B[2])
+
+    @staticmethod
+    def of(arr, B: "Param") -> "MatMat":
+        P, K = B.base_shape
+        if arr.shape[1] != P:
+            raise TraceError(f"X @ B: X has {arr.shape[1]} columns, B {P} rows; " + _SOFTMAX_FORM)
+        return MatMat(np.ascontiguousarray(arr, np.float32), (B.offset, P, K))
+
+    def __add__(self, other):
+        K = self.shape[1]
+        if isinstance(other, Param):
+            if (other.view is not None or other.xf or other.base_shape != (K,)
+                    or self.icpt is not None):
+                raise TraceError(f"X @ B plus {other!r} (a scalar parameter moves every class "
+                                 "alike and cancels in the softmax; the class intercepts are one "
+                                 f"whole, untransformed 1-D parameter of {K} elements): "
+                                 + _SOFTMAX_FORM)
+            return MatMat(self.X, self.B, other.offset)
+        if is_symbolic(other):
+            raise TraceError("X @ B inside another expression: " + _SOFTMAX_FORM)
+        raise TraceError("X @ B plus a data vector or a constant (a value added to every class "
+                         "of a row cancels in the softmax; per-class data offsets are not "
+                         "taken): " + _SOFTMAX_FORM)
+
+    __radd__ = __add__
+
+    def _inside(self, *a, **k):
+        raise TraceError("X @ B inside another expression (only + a, the class intercepts, "
+                         "extends it): " + _SOFTMAX_FORM)
+
+    __sub__ = __rsub__ = __mul__ = __rmul__ = __truediv__ = __rtruediv__ = _inside
+    __pow__ = __rpow__ = __neg__ = __abs__ = __getitem__ = __matmul__ = __rmatmul__ = _inside
+    __lt__ = __le__ = __gt__ = __ge__ = __float__ = __bool__ = _inside
+
+    def refuse_as_beta(self, name: str):
+        """Normal / Bernoulli / Poisson over X @ B: their beta is a vector."""
+        raise TraceError(f"{name} over X @ B with a multi-dimensional parameter B (only "
+                         "Categorical(logits=X @ B) takes a matrix of coefficients): " + _GLM_FORM)
+
+    def __repr__(self):
+        return f"MatMat(X{list(self.X.shape)} @ params[{self.B[0]}:+{self.B[1]}x{self.B[2]}])"
+
+
 @dataclass
 class GlmSpec:
-    """The design-matrix likelihood of a traced model (mc_glm)."""
+    """The design-matrix likelihood of a traced model (mc_glm; mc_glm_softmax when
+    eta is a MatMat)."""
     family: int
-    eta: MatVec
+    eta: Union[MatVec, MatMat]
     y: np.ndarray
     scale: Optional["Operand"] = None  # the normal family's scale
     lp_const: float = 0.0              # the count normaliser's sum (Poisson)
+
+    @property
+    def softmax(self) -> bool:
+        return self.family == _lib.MC_GLM_CATEGORICAL_LOGIT
 
     @property
     def N(self) -> int:
@@ -414,6 +489,35 @@ def glm_term(name: str, eta: MatVec, value, scale=None) -> "LogProbExpr":
         spec.lp_const = float(np.sum(discrete_norm("Poisson", y), dtype=np.float64))
     term = Term(GLM_DIST, NONE_OPERAND, NONE_OPERAND, NONE_OPERAND, spec.N, glm=spec)
     return LogProbExpr([term], 0.0, eta.shape)
+
+
+def softmax_term(logits: MatMat, value) -> "LogProbExpr":
+    """Categorical(logits=X @ B [+ a]).log_prob(y): one term, summed whole by
+    mx.sum.  The limits on K and P are checked here, where the matrix meets the
+    family that takes it; y is concrete, so the labels are checked here too and
+    the kernel has no invalid-label path."""
+    N, K = logits.shape
+    P = logits.B[1]
+    if not 2 <= K <= _lib.MC_GLM_SOFTMAX_MAX_K:
+        raise TraceError(f"Categorical(logits=X @ B) with K = {K} classes (one class is a "
+                         "constant; the classes of a chain share one 32-column gradient "
+                         "block): " + _SOFTMAX_FORM)
+    if P > _lib.MC_GLM_MAX_P:
+        raise TraceError(f"Categorical(logits=X @ B) with P = {P} columns: " + _SOFTMAX_FORM)
+    if is_symbolic(value):
+        raise TraceError("Categorical(logits=X @ B).log_prob of a traced value: " + _SOFTMAX_FORM)
+    y = np.asarray(_to_numpy(value))
+    if y.dtype == object or y.dtype.kind not in "fiub" or y.shape != (N,):
+        raise TraceError(f"Categorical(logits=X @ B).log_prob(y) with y of shape {y.shape}, X of "
+                         f"{N} rows: " + _SOFTMAX_FORM)
+    yf = y.astype(np.float64)
+    bad = np.flatnonzero(~((yf >= 0) & (yf < K) & (yf == np.floor(yf))))
+    if bad.size:
+        raise TraceError(f"Categorical(logits=X @ B).log_prob(y): y[{bad[0]}] = {y[bad[0]]} is "
+                         f"not an integer label in 0 .. {K - 1}; " + _SOFTMAX_FORM)
+    spec = GlmSpec(_lib.MC_GLM_CATEGORICAL_LOGIT, logits, np.ascontiguousarray(yf, np.float32))
+    term = Term(GLM_DIST, NONE_OPERAND, NONE_OPERAND, NONE_OPERAND, N, glm=spec)
+    return LogProbExpr([term], 0.0, (N,))
 
 
 def _is_slope(x) -> bool:
@@ -620,6 +724,8 @@ class Expr:
             return x
         if isinstance(x, MatVec):
             raise TraceError("a matvec inside another expression: " + _GLM_FORM)
+        if isinstance(x, MatMat):
+            x._inside()
         if isinstance(x, LogProbExpr):
             raise TraceError("a log density inside a parameter expression or as a distribution "
                              "argument (only + / - / scalar * / mx.sum / mx.mean combine log "
@@ -676,12 +782,12 @@ class Expr:
 
     # -- arithmetic ------------------------------------------------------------
     def __add__(self, other):
-        if isinstance(other, (LogProbExpr, MatVec)):
+        if isinstance(other, (LogProbExpr, MatVec, MatMat)):
             return other + self
         return Expr.binary(_lib.MC_EX_ADD, self, other)
 
     def __radd__(self, other):
-        if isinstance(other, (LogProbExpr, MatVec)):
+        if isinstance(other, (LogProbExpr, MatVec, MatMat)):
             return other + self
         return Expr.binary(_lib.MC_EX_ADD, other, self)
 
@@ -866,12 +972,14 @@ def discrete_expr(name: str, value, total, arg, natural: bool) -> "LogProbExpr":
     is the logit / log rate; otherwise it is a probability p or a rate r and
     the node sits on eta = log p - log1p(-p) inside where(p > 0, where(p < 1,
     ., -inf), -inf), or theta = log r inside where(r > 0, ., -inf)."""
+    if isinstance(arg, MatMat):
+        arg.refuse_as_beta(name)
     if isinstance(arg, MatVec):
         if name == "Binomial" or not natural:
             raise TraceError(f"{name} over X @ beta in its probs= / rate= form (or Binomial): "
                              "pass the linear predictor as logits= / log_rate=; " + _GLM_FORM)
         return glm_term(name, arg, value)
-    if any(isinstance(x, MatVec) for x in (value, total)):
+    if any(isinstance(x, (MatVec, MatMat)) for x in (value, total)):
         raise TraceError(f"X @ beta as {name}'s value or total_count: " + _GLM_FORM)
     op = _DISCRETE_OP[name]
     y = _concrete_f32(name, "value", value)
@@ -1053,6 +1161,8 @@ def to_operand(x) -> Operand:
                            transform=xf)
         return Operand(_lib.MC_OP_GATHER, param_offset=x.offset, index=v[1], shape=tuple(v[2]),
                        transform=xf)
+    if isinstance(x, MatMat):
+        x.refuse_as_beta("this distribution")
     if isinstance(x, MatVec):
         raise TraceError("X @ beta as this distribution argument: " + _GLM_FORM)
     if isinstance(x, LogProbExpr):
@@ -1076,7 +1186,7 @@ def to_operand(x) -> Operand:
 
 
 def is_symbolic(*xs) -> bool:
-    return any(isinstance(x, (Param, LogProbExpr, Affine, Expr, MatVec)) for x in xs)
+    return any(isinstance(x, (Param, LogProbExpr, Affine, Expr, MatVec, MatMat)) for x in xs)
 
 
 @dataclass
@@ -1326,6 +1436,9 @@ def _scalar_const(x) -> float:
 
 
 def make_term(dist: int, dist_name: str, value, loc, scale) -> LogProbExpr:
+    for x in (value, loc, scale):
+        if isinstance(x, MatMat):
+            x.refuse_as_beta(dist_name)
     if any(isinstance(x, MatVec) for x in (value, loc, scale)):
         if dist_name != "Normal" or not isinstance(loc, MatVec):
             raise TraceError(f"X @ beta as an argument of {dist_name} other than Normal's loc: "
@@ -1542,6 +1655,14 @@ def _glm_model(layout: "ParamLayout", terms: List[Term], const: float) -> Traced
     model = TracedModel(layout, priors, float(np.float32(const + spec.lp_const)))
     _build_pools(model)
     eta = spec.eta
+    if spec.softmax:
+        g = _lib.McGlmSoftmax()
+        g.beta_offset, g.n, g.p, g.k = eta.B[0], spec.N, eta.B[1], eta.B[2]
+        g.icpt_offset = -1 if eta.icpt is None else eta.icpt
+        g.x_pool, g.y_pool = 0, spec.N * spec.P
+        model.data = np.concatenate([eta.X.ravel(), spec.y]).astype(np.float32)
+        model.glm, model.c_glm = spec, g
+        return model
     N, P = spec.N, spec.P
     g = _lib.McGlm()
     g.family, g.beta_offset, g.n, g.p = spec.family, eta.beta[0], N, P
@@ -1713,7 +1834,9 @@ class Program:
         index = np.ascontiguousarray(model.index, np.int32)
         dp = data.ctypes.data_as(ctypes.c_void_p)
         if model.glm is not None:
-            create = (lib.mc_program_create_glm_wide if glm_kernel == "wide"
+            refuse_softmax(model, "glm_kernel='wide'" if glm_kernel == "wide" else None)
+            create = (lib.mc_program_create_glm_softmax if model.glm.softmax
+                      else lib.mc_program_create_glm_wide if glm_kernel == "wide"
                       else lib.mc_program_create_glm)
             _lib.check(create(
                 ctypes.byref(model.c_glm), model.c_terms, len(model.terms), self.D,
@@ -1995,6 +2118,19 @@ def refuse_glm(model: TracedModel, what: str) -> None:
                          "when asked to: loo(..., loo_kernel='glm'))")
 
 
+def refuse_softmax(model: TracedModel, what: Optional[str]) -> None:
+    """Softmax regression (Categorical(logits=X @ B)) runs on k_glm_softmax_grad
+    under hmc() and logp_grad only: what the other design-matrix models opt in to
+    raises before any device work."""
+    if what is not None and model.glm is not None and model.glm.softmax:
+        raise ValueError(f"{what}: softmax regression (Categorical(logits=X @ B)) runs under "
+                         "hmc() / MCMC.run(method='hmc') on k_glm_softmax_grad without a mass "
+                         "matrix; the column-split kernel (glm_kernel='wide'), NUTS "
+                         "(nuts_kernel='glm'), pointwise_log_likelihood / waic, "
+                         "posterior_predictive(predictive_kernel='glm') and "
+                         "loo(loo_kernel='glm') do not take it yet")
+
+
 _GLM_POINTWISE_FORM = (
     "the pointwise log-likelihood of a design-matrix model is exactly one "
     "mx.sum(Family(X @ beta ...).log_prob(y)), passed alone: priors and other terms belong "
@@ -2019,6 +2155,7 @@ def compile_model(log_prob_fn, initial_params: dict, slices: int = 0,
     model = trace(log_prob_fn, initial_params)
     if glm is not None:
         refuse_glm(model, glm)
+    refuse_softmax(model, "glm_kernel='wide'" if glm_kernel == "wide" else require_glm)
     if glm_kernel == "wide" and require_glm is None:
         require_glm = "glm_kernel='wide'"
     if require_glm is not None and model.glm is None:
@@ -2060,6 +2197,7 @@ def pointwise_program(log_likelihood_fn, layout: ParamLayout,
     model = trace(log_likelihood_fn, init, keep_order=True)
     if glm is not None:
         refuse_glm(model, glm)
+    refuse_softmax(model, require_glm or "the pointwise log-likelihood (waic, loo, predictive)")
     if require_glm is not None and model.glm is None:
         raise ValueError(f"{require_glm} takes a design-matrix likelihood only: "
                          + _GLM_POINTWISE_FORM)

@@ -75,6 +75,10 @@ struct GlmDev {
     float sval;
     float c0;  // normal: -0.5 log(2 pi)
     float lp_const;
+    // MC_GLM_CATEGORICAL_LOGIT (glm_softmax.h): K classes padded to Kp (a power of
+    // two), CPB = 32 / Kp chains per gradient block; B[p, k] is parameter boff +
+    // p K + k, the class intercepts aoff .. aoff + K (aoff < 0: none)
+    int32_t K, Kp, CPB, aoff;
 };
 
 typedef float glm_acc __attribute__((ext_vector_type(16)));
@@ -207,6 +211,7 @@ struct GlmPart {
     const float* part;  // slot (slice 0, this chain block)
     int64_t stride;     // floats between the slices of a chain block
     int S;
+    int col;            // softmax: the chain's first column (class 0) in its block
 };
 
 MC_DEV float glm_part_sum(const GlmPart& R, int row, int j) {
@@ -215,8 +220,37 @@ MC_DEV float glm_part_sum(const GlmPart& R, int row, int j) {
     return x;
 }
 
+// The partials of chain c = 32 cb + j of a launch: the chain block's slot, or
+// for a softmax program (glm_softmax.h: CPB chains per gradient block, class-
+// minor columns) the slot of gradient block c / CPB and the chain's first column.
+MC_DEV GlmPart glm_part_of(const GlmDev& G, GlmPart R, int cb, int64_t c) {
+    const int64_t blk = (int64_t)(G.Pp + kGlmExtra) * 32;
+    if (G.family == MC_GLM_CATEGORICAL_LOGIT) {
+        R.part += (c / G.CPB) * blk;
+        R.col = (int)(c % G.CPB) * G.Kp;
+    } else {
+        R.part += (int64_t)cb * blk;
+    }
+    return R;
+}
+
+// the chain's log likelihood: row Pp + 2 of its column, or of its K class columns
+// in class order
+MC_DEV float glm_part_lp(const GlmDev& G, const GlmPart& R, int j) {
+    if (G.family != MC_GLM_CATEGORICAL_LOGIT) return glm_part_sum(R, G.Pp + 2, j);
+    float l = 0.0f;
+    for (int k = 0; k < G.K; ++k) l += glm_part_sum(R, G.Pp + 2, R.col + k);
+    return l;
+}
+
 // d log likelihood / d q[d] of chain j (qd = q[d])
 MC_DEV float glm_like_grad(const GlmDev& G, const GlmPart& R, int j, int d, float qd) {
+    if (G.family == MC_GLM_CATEGORICAL_LOGIT) {
+        const int e = d - G.boff, a = d - G.aoff;
+        if (e >= 0 && e < G.P * G.K) return glm_part_sum(R, e / G.K, R.col + e % G.K);
+        if (G.aoff >= 0 && a >= 0 && a < G.K) return glm_part_sum(R, G.Pp, R.col + a);
+        return 0.0f;
+    }
     float g = 0.0f;
     if (d >= G.boff && d < G.boff + G.P) g += glm_part_sum(R, d - G.boff, j);
     if (G.ik == MC_OP_PSCALAR && d == G.ipoff) g += glm_part_sum(R, G.Pp, j);
@@ -265,8 +299,7 @@ k_glm_finish(GlmDev G, int64_t C, const float* q, GlmPart R0, float* logp, float
     const int64_t c = (int64_t)cb * kGlmChains + j;
     const bool live = c < C;
     const int D = G.D;
-    GlmPart R = R0;
-    R.part += (int64_t)cb * ((G.Pp + kGlmExtra) * 32);
+    const GlmPart R = glm_part_of(G, R0, cb, c);
     float lpp = 0.0f;
     if (live) {
         GLM_FOR_OWNED(D) {
@@ -279,7 +312,7 @@ k_glm_finish(GlmDev G, int64_t C, const float* q, GlmPart R0, float* logp, float
     }
     const float lps = glm_chain_sum(lpp, red, pr, j);
     if (live && pr == 0) {
-        const float lp = (G.lp_const + glm_part_sum(R, G.Pp + 2, j)) + lps;
+        const float lp = (G.lp_const + glm_part_lp(G, R, j)) + lps;
         if constexpr (INIT) {
             mc_chain_scalars sc = {};
             sc.step_size = eps0;
@@ -318,8 +351,7 @@ k_glm_hmc_step(GlmDev G, RunArgs A, int phase, int64_t it, mc_chain_scalars* sca
     const int L = cfg.num_leapfrog_steps;
     float* qt = qT + (int64_t)cb * D * 32 + j;  // element d at qt[d * 32]
     float* pt = pT + (int64_t)cb * D * 32 + j;
-    GlmPart R = R0;
-    R.part += (int64_t)cb * ((G.Pp + kGlmExtra) * 32);
+    const GlmPart R = glm_part_of(G, R0, cb, c);
     const double eps = live ? scal[c].step_size : 0.0;
     const float lp = live ? scal[c].logp : 0.0f;  // (read before thread 0 of the chain updates it)
     const float h = (float)(0.5 * eps);
@@ -386,7 +418,7 @@ k_glm_hmc_step(GlmDev G, RunArgs A, int phase, int64_t it, mc_chain_scalars* sca
     const float ks = glm_chain_sum(kp1, red, pr, j);
     const float lps = glm_chain_sum(lpp, red, pr, j);
     if (!live) return;
-    const float lpn = L > 0 ? (G.lp_const + glm_part_sum(R, G.Pp + 2, j)) + lps : lp;
+    const float lpn = L > 0 ? (G.lp_const + glm_part_lp(G, R, j)) + lps : lp;
     const float H1 = -lpn + 0.5f * ks;
     const float Hi = H0[c];
     const float ratio = -(H1 - Hi);
@@ -453,6 +485,9 @@ struct GlmPlan {
     // every wave owning PTW 32-wide coefficient tiles: Pp = 128 PTW, PT = 4 PTW
     bool wide = false;
     int PTW = 0;
+    // mc_program_create_glm_softmax: family MC_GLM_CATEGORICAL_LOGIT on
+    // k_glm_softmax_grad (glm_softmax.h), dev.CPB chains per gradient block
+    bool softmax = false;
     int slices = 0;           // mc_program_set_slices: 0 automatic, else 1 .. 64
     // partials of mc_logp_grad / mc_state_init, which take no workspace: room for
     // kScratchBlocks chain blocks of 64 slices, used in stream order
@@ -471,9 +506,15 @@ constexpr int kGlmMaxSlices = 64;
 inline int64_t glm_block_floats(const GlmPlan* g) {
     return (int64_t)(g->dev.Pp + mc::kGlmExtra) * mc::kGlmChains;
 }
+// gradient blocks of a launch of C chains: 32 chains each, CPB on a softmax plan
+inline int64_t glm_grad_blocks(const GlmPlan* g, int64_t C) {
+    const int64_t per = g->softmax ? g->dev.CPB : mc::kGlmChains;
+    return (C + per - 1) / per;
+}
 // row slices of a launch of C chains (plan_glm.hip)
 int glm_plan_slices(const GlmPlan* g, int64_t C);
-// k_glm_grad, or k_glm_grad_wide on a wide plan, at the positions q (strides sc,
-// sp: above) of C chains, S slices (run_glm.hip)
+// k_glm_grad, k_glm_grad_wide on a wide plan or k_glm_softmax_grad on a softmax
+// plan, at the positions q (strides sc, sp: above) of C chains, S slices
+// (run_glm.hip)
 int glm_launch_grad(const GlmPlan* g, const float* q, int sc, int sp, int64_t C, int S, float* part,
                     hipStream_t st);

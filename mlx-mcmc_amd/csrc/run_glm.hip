@@ -1,6 +1,8 @@
 // run_glm.hip — launches of the design-matrix kernels (glm.h): mc_logp_grad,
-// mc_state_init and mc_hmc_run of a program made by mc_program_create_glm or
-// mc_program_create_glm_wide (the gradient then runs on glm_wide.h's kernel).
+// mc_state_init and mc_hmc_run of a program made by mc_program_create_glm,
+// mc_program_create_glm_wide (the gradient then runs on glm_wide.h's kernel) or
+// mc_program_create_glm_softmax (on glm_softmax.h's, whose gradient blocks hold
+// CPB = 32 / Kp chains: the partial blocks are counted by glm_grad_blocks).
 //
 // mc_hmc_run enqueues, per iteration, one k_glm_hmc_step for the iteration
 // start, then per leapfrog step one k_glm_grad and one k_glm_hmc_step, in stream
@@ -11,6 +13,7 @@
 // launches.  No host synchronisation and no allocation inside the call.
 #include "launch.h"
 #include "glm_wide.h"
+#include "glm_softmax.h"
 
 static int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
@@ -27,7 +30,8 @@ static GlmWs glm_ws(const mc_program* p, int64_t C, int S) {
     w.p = vec;
     w.h0 = 2 * vec;
     w.part = w.h0 + align256(blocks * kGlmChains * 4);
-    w.total = w.part + align256((int64_t)S * blocks * glm_block_floats(p->glm) * 4);
+    w.total = w.part + align256((int64_t)S * glm_grad_blocks(p->glm, C) *
+                                glm_block_floats(p->glm) * 4);
     return w;
 }
 
@@ -77,10 +81,41 @@ static int launch_wide_fam(const GlmPlan* g, const float* q, int sc, int sp, int
         default: return fail(MC_ERR_INVALID, "k_glm_grad_wide has no instantiation PTW = %d", g->PTW);
     }
 }
-// k_glm_grad, or k_glm_grad_wide on a wide plan, at the positions q (strides sc,
-// sp: glm.h) of C chains, S slices
+template <int PT, int KP>
+static int launch_softmax_kp(const GlmPlan* g, const float* q, int sc, int sp, int64_t C, int S,
+                             float* part, hipStream_t st) {
+    const int64_t blocks = glm_grad_blocks(g, C);
+    const size_t lds = (size_t)PT * 1024 * 4;
+    hipLaunchKernelGGL((k_glm_softmax_grad<PT, KP>), dim3((unsigned)S, (unsigned)blocks), dim3(256),
+                       lds, st, g->dev, q, sc, sp, C, S, part);
+    MC_HIP_TRY(hipGetLastError());
+    return MC_OK;
+}
+template <int PT>
+static int launch_softmax_pt(const GlmPlan* g, const float* q, int sc, int sp, int64_t C, int S,
+                             float* part, hipStream_t st) {
+    switch (g->dev.Kp) {
+        case 2: return launch_softmax_kp<PT, 2>(g, q, sc, sp, C, S, part, st);
+        case 4: return launch_softmax_kp<PT, 4>(g, q, sc, sp, C, S, part, st);
+        case 8: return launch_softmax_kp<PT, 8>(g, q, sc, sp, C, S, part, st);
+        case 16: return launch_softmax_kp<PT, 16>(g, q, sc, sp, C, S, part, st);
+        case 32: return launch_softmax_kp<PT, 32>(g, q, sc, sp, C, S, part, st);
+        default: return fail(MC_ERR_INVALID, "k_glm_softmax_grad has no instantiation Kp = %d",
+                             g->dev.Kp);
+    }
+}
+// k_glm_grad, k_glm_grad_wide on a wide plan or k_glm_softmax_grad on a softmax
+// plan, at the positions q (strides sc, sp: glm.h) of C chains, S slices
 static int launch_grad(const GlmPlan* g, const float* q, int sc, int sp, int64_t C, int S,
                        float* part, hipStream_t st) {
+    if (g->softmax) {
+        switch (g->PT) {
+            case 1: return launch_softmax_pt<1>(g, q, sc, sp, C, S, part, st);
+            case 2: return launch_softmax_pt<2>(g, q, sc, sp, C, S, part, st);
+            case 4: return launch_softmax_pt<4>(g, q, sc, sp, C, S, part, st);
+            default: return launch_softmax_pt<8>(g, q, sc, sp, C, S, part, st);
+        }
+    }
     if (g->wide) {
         switch (g->dev.family) {
             case MC_GLM_NORMAL: return launch_wide_fam<MC_GLM_NORMAL>(g, q, sc, sp, C, S, part, st);
@@ -97,14 +132,15 @@ static int launch_grad(const GlmPlan* g, const float* q, int sc, int sp, int64_t
     }
 }
 
-// One gradient launch and its reduce, in chunks of kGlmScratchBlocks chain
-// blocks on the program's scratch (stream order makes the reuse safe).
+// One gradient launch and its reduce, in chunks of kGlmScratchBlocks gradient
+// blocks (32 chains each, CPB on a softmax plan) on the program's scratch
+// (stream order makes the reuse safe).
 template <bool INIT>
 static int glm_eval(const mc_program* p, int64_t n, const float* q, float* lp, float* grad,
                     double eps0, mc_chain_scalars* scal, float* st_q, hipStream_t st) {
     const GlmPlan* g = p->glm;
     const int S = glm_plan_slices(g, n);
-    const int64_t chunk = (int64_t)kGlmScratchBlocks * kGlmChains;
+    const int64_t chunk = (int64_t)kGlmScratchBlocks * (g->softmax ? g->dev.CPB : kGlmChains);
     const float mu = mc_logf_ref((float)(10.0 * eps0));  // nuts.py:63, as k_init
     for (int64_t c0 = 0; c0 < n; c0 += chunk) {
         const int64_t nc = std::min(chunk, n - c0);
@@ -112,7 +148,7 @@ static int glm_eval(const mc_program* p, int64_t n, const float* q, float* lp, f
         const float* qc = q + c0 * p->D;
         const int rc = launch_grad(g, qc, p->D, 1, nc, S, g->d_scratch, st);
         if (rc != MC_OK) return rc;
-        const GlmPart R = {g->d_scratch, blocks * glm_block_floats(g), S};
+        const GlmPart R = {g->d_scratch, glm_grad_blocks(g, nc) * glm_block_floats(g), S, 0};
         hipLaunchKernelGGL((k_glm_finish<INIT>), dim3((unsigned)blocks), dim3(256), 0, st, g->dev,
                            nc, qc, R, lp ? lp + c0 : nullptr, grad + c0 * p->D, eps0, mu,
                            scal ? scal + c0 : nullptr, st_q ? st_q + c0 * p->D : nullptr);
@@ -157,7 +193,7 @@ int glm_hmc_run(const mc_program* p, const mc_run_config* cfg, void* state, floa
     float* H0 = (float*)(b + W.h0);
     float* part = (float*)(b + W.part);
     const int64_t blocks = (C + kGlmChains - 1) / kGlmChains;
-    const GlmPart RP = {part, blocks * glm_block_floats(g), S};
+    const GlmPart RP = {part, glm_grad_blocks(g, C) * glm_block_floats(g), S, 0};
     const int L = cfg->num_leapfrog_steps;
     auto step = [&](int phase, int64_t it) {
         hipLaunchKernelGGL((k_glm_hmc_step<0>), dim3((unsigned)blocks), dim3(256), 0, st, g->dev, R.A,

@@ -58,7 +58,8 @@ extern "C" int mc_debug_glm_nuts_stats(int64_t* ticks, int64_t* polls) {
 }
 
 extern "C" int64_t mc_nuts_glm_workspace_bytes(const mc_program* p, int64_t C, int32_t max_depth) {
-    if (!is_glm(p) || C < 0 || max_depth < 0 || max_depth > kMaxTreeDepth) return -1;
+    if (!is_glm(p) || p->glm->softmax || C < 0 || max_depth < 0 || max_depth > kMaxTreeDepth)
+        return -1;
     return glm_nuts_ws(p, C, max_depth, glm_plan_slices(p->glm, C)).total;
 }
 
@@ -70,6 +71,10 @@ extern "C" int mc_nuts_run_glm(const mc_program* p, const mc_run_config* cfg, vo
     if (!is_glm(p))
         return fail(MC_ERR_UNSUPPORTED, "mc_nuts_run_glm runs design-matrix (X @ beta) programs "
                     "(mc_program_create_glm) only: mc_nuts_run runs this one");
+    if (p->glm->softmax)
+        return fail(MC_ERR_UNSUPPORTED, "mc_nuts_run_glm: a softmax program "
+                    "(mc_program_create_glm_softmax) runs under mc_hmc_run only: k_glm_nuts_step "
+                    "reads one column per chain, not the class-packed gradient blocks");
     if (cfg->max_tree_depth < 0 || cfg->max_tree_depth > kMaxTreeDepth)
         return fail(MC_ERR_UNSUPPORTED, "max_tree_depth must be in [0, %d]", kMaxTreeDepth);
     const GlmPlan* g = p->glm;
@@ -93,7 +98,7 @@ extern "C" int mc_nuts_run_glm(const mc_program* p, const mc_run_config* cfg, vo
     float* part = (float*)(b + W.part);
     const int64_t blocks = (C + kGlmChains - 1) / kGlmChains;
     int32_t* d_left = cnt + blocks;
-    const GlmPart RP = {part, blocks * glm_block_floats(g), S};
+    const GlmPart RP = {part, blocks * glm_block_floats(g), S, 0};
     auto step = [&](int phase) {
         hipLaunchKernelGGL((k_glm_nuts_step<0>), dim3((unsigned)blocks), dim3(256), 0, st, g->dev,
                            R.A, phase, R.scalars, R.q, R.g, samples, td, qT, arena, words, cnt, RP);

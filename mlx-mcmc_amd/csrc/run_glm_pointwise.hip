@@ -19,6 +19,11 @@ int64_t glm_pw_elements(const mc_program* p) { return p->glm->dev.N; }
 int glm_pw_enable(mc_program* p) {
     GlmPlan* g = p->glm;
     if (g->d_norm) return MC_OK;
+    if (g->softmax)
+        return fail(MC_ERR_UNSUPPORTED,
+                    "pointwise: a softmax program (mc_program_create_glm_softmax) has no pointwise "
+                    "view yet: k_glm_pointwise forms one linear predictor per draw, not K class "
+                    "logits");
     if (g->wide)
         return fail(MC_ERR_UNSUPPORTED,
                     "pointwise: a program of mc_program_create_glm_wide (glm_kernel=\"wide\") has no "

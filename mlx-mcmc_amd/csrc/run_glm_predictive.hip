@@ -22,6 +22,10 @@ int gpp_plan(const mc_program* p, int64_t C, int64_t S, int64_t thin, GppPlan* o
                     "(X @ beta) program of mc_program_create_glm; mc_predictive takes every "
                     "other likelihood");
     const GlmPlan* g = p->glm;
+    if (g->softmax)
+        return fail(MC_ERR_UNSUPPORTED, "glm predictive: a softmax program "
+                    "(mc_program_create_glm_softmax) is not taken: k_glm_predictive forms one "
+                    "linear predictor per draw, not K class logits");
     if (g->wide)
         return fail(MC_ERR_UNSUPPORTED,
                     "glm predictive: a program of mc_program_create_glm_wide (glm_kernel=\"wide\") "

@@ -23,6 +23,10 @@ int gps_plan(const mc_program* p, int64_t C, int64_t S, double r_eff, GpsPlan* o
                     "(X @ beta) program of mc_program_create_glm; mc_psis_loo takes every "
                     "other likelihood");
     const GlmPlan* g = p->glm;
+    if (g->softmax)
+        return fail(MC_ERR_UNSUPPORTED, "glm psis: a softmax program "
+                    "(mc_program_create_glm_softmax) is not taken: the select and gather kernels "
+                    "form one linear predictor per draw, not K class logits");
     if (g->wide)
         return fail(MC_ERR_UNSUPPORTED,
                     "glm psis: a program of mc_program_create_glm_wide (glm_kernel=\"wide\") is "

@@ -482,8 +482,12 @@ def pointwise_log_likelihood(log_likelihood_fn, samples, layout=None, *, matrix=
 
     from . import _trace
 
-    x, lay = _pointwise_inputs(samples, layout)
-    part, mat = _pointwise_launch(_trace.pointwise_program(log_likelihood_fn, lay), x, matrix)
+    # (the likelihood is traced, and a form with no pointwise view refused, before
+    # the device is asked for)
+    draws, lay = _pointwise_host_inputs(samples, layout)
+    prog = _trace.pointwise_program(log_likelihood_fn, lay)
+    x, lay = _pointwise_inputs(draws, lay)
+    part, mat = _pointwise_launch(prog, x, matrix)
     out = merge_pointwise(_gather_parts(part, group))
     if matrix:
         out["matrix"] = mat
@@ -737,8 +741,7 @@ def posterior_predictive(log_likelihood_fn, samples, layout=None, *, seed=0, thi
     thin = int(thin)
     if thin < 1:
         raise ValueError("thin must be >= 1")
-    x, lay = _pointwise_inputs(samples, layout)
-    C, S, D = x.shape
+    draws, lay = _pointwise_host_inputs(samples, layout)
     glm = predictive_kernel == "glm"
     if glm:
         prog = _trace.pointwise_program(log_likelihood_fn, lay,
@@ -747,6 +750,8 @@ def posterior_predictive(log_likelihood_fn, samples, layout=None, *, seed=0, thi
         prog = _trace.pointwise_program(log_likelihood_fn, lay,
                                         glm="posterior predictive replicates "
                                             "(diagnostics.posterior_predictive)")
+    x, lay = _pointwise_inputs(draws, lay)
+    C, S, D = x.shape
     lib = _lib.load()
     M = prog.num_elements
     size = lib.mc_glm_predictive_workspace_bytes if glm else lib.mc_predictive_workspace_bytes

@@ -475,6 +475,12 @@ class Categorical(Distribution):
         ``[0.0, a1 + b1 * x, a2 + b2 * x]``.  Entries are scalars or share one
         shape.
 
+    ``logits=X @ B [+ a]`` with X a data matrix [N, P], B a whole 2-D parameter
+    [P, K] and a a whole 1-D parameter of K class intercepts is softmax
+    regression on a design matrix: 2 <= K <= 32 classes, P <= 256 columns, on the
+    class-packed MFMA gradient kernel of csrc/glm_softmax.h under ``hmc()``
+    (_trace.softmax_term), not an expression term.
+
     ``log_prob(value)`` with a traced argument records one expression term of
     3K + 2 nodes over scalar classes (_trace.categorical_expr); value is data
     or a constant.  A term holds at most 32 nodes: K <= 10 scalar classes,
@@ -496,6 +502,16 @@ class Categorical(Distribution):
             raise ValueError("Categorical takes one of probs= / logits= (got both)")
         self._natural = logits is not None
         arg = logits if self._natural else probs
+        self._matmat = arg if isinstance(arg, _trace.MatMat) else None
+        if self._matmat is not None:
+            # softmax regression on a design matrix (csrc/glm_softmax.h)
+            if not self._natural:
+                raise _trace.TraceError("Categorical(probs=X @ B): the class logits of a design "
+                                        "matrix are passed as logits=; " + _trace._SOFTMAX_FORM)
+            self._entries, self._traced = [], True
+            self.num_categories = arg.shape[1]
+            self.probs, self.logits = None, logits
+            return
         self._entries = self._classes(arg)
         self._traced = _trace.is_symbolic(*self._entries)
         self.num_categories = len(self._entries)
@@ -535,6 +551,8 @@ class Categorical(Distribution):
         return [a[k] for k in range(a.shape[0])]
 
     def log_prob(self, value):
+        if self._matmat is not None:
+            return _trace.softmax_term(self._matmat, value)
         if self._traced or _trace.is_symbolic(value):
             return _trace.categorical_expr(value, self._entries, self._natural)
         v = np.asarray(_trace._to_numpy(value))

@@ -276,6 +276,8 @@ def run_sampler(algorithm: str, log_prob_fn, initial_params, *, num_samples: int
     if program.model.glm is not None:
         info.extra["glm_slices"] = program.glm_slices(C)
         info.extra["glm_kernel"] = program.glm_kernel
+        info.extra["glm_family"] = ("normal", "bernoulli", "poisson",
+                                    "categorical")[program.model.glm.family]
     if algorithm == "hmc" and not use_metric and program.hmc_dense:
         # (slices, slots) of the dense route: a chain pair per workgroup
         info.extra["hmc_dense"] = program.hmc_dense

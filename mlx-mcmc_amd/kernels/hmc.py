@@ -30,7 +30,10 @@ metric, which a second run can start from.
 columns on ``k_glm_grad`` (csrc/glm.h) and refuses a wider one; "wide" runs it on
 the column-split kernel ``k_glm_grad_wide`` (csrc/glm_wide.h: up to 1024 columns,
 a quarter of the gradient block's registers per lane), and raises ``ValueError``
-for a model that is not a design-matrix model.
+for a model that is not a design-matrix model.  Softmax regression
+(``Categorical(logits=X @ B [+ a])``, B a ``[P, K]`` parameter, K <= 32, P <= 256)
+runs on ``k_glm_softmax_grad`` (csrc/glm_softmax.h) under "auto" only
+(``RunInfo.extra["glm_family"] == "categorical"``).
 Vector-valued parameters are supported (the reference's ``float()`` store,
 hmc.py:192, rejects them — SURVEY Q6).
 """
