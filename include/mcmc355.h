@@ -1261,10 +1261,17 @@ int mc_program_create_glm_wide(const mc_glm* glm, const mc_term* priors, int32_t
  * mc_hmc_run / mc_hmc_workspace_bytes, mc_program_set_slices / _num_slices /
  * _glm_slices / _kernel_note / _num_params / _destroy, with the guarantees of
  * mc_program_create_glm (a chain's draws do not depend on the split of the
- * chains; two calls give the same bits).  mc_nuts_run_glm,
- * mc_program_enable_pointwise, mc_glm_predictive and mc_glm_psis_loo return
- * MC_ERR_UNSUPPORTED for it, as every entry that refuses a design-matrix
- * program does.                                                              */
+ * chains; two calls give the same bits).  A program WITHOUT prior terms also
+ * takes mc_program_num_elements (n), mc_program_enable_pointwise,
+ * mc_pointwise_workspace_bytes and mc_pointwise_stats, arguments and statistics
+ * as for mc_program_create_glm: the value of observation i under a draw is the
+ * f32 log softmax(eta_i)[y_i] = e - (m + log sum_k exp(e_k - m)), m the largest
+ * logit, the logits from the MFMA product of csrc/glm_softmax_pointwise.h with
+ * (draw, class) pairs as its columns; a NaN logit of any class makes the value
+ * NaN.  mc_nuts_run_glm, mc_glm_predictive and mc_glm_psis_loo (their
+ * workspace queries included) return MC_ERR_UNSUPPORTED for it, with or without
+ * the pointwise view, as every entry that refuses a design-matrix program
+ * does.                                                                      */
 #define MC_GLM_CATEGORICAL_LOGIT 3
 #define MC_GLM_SOFTMAX_MAX_K     32
 typedef struct mc_glm_softmax {

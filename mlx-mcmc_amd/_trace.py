@@ -2120,15 +2120,17 @@ def refuse_glm(model: TracedModel, what: str) -> None:
 
 def refuse_softmax(model: TracedModel, what: Optional[str]) -> None:
     """Softmax regression (Categorical(logits=X @ B)) runs on k_glm_softmax_grad
-    under hmc() and logp_grad only: what the other design-matrix models opt in to
-    raises before any device work."""
+    under hmc() and logp_grad, and its likelihood alone under the pointwise / WAIC
+    entry points when asked to (pointwise_kernel='glm'): whatever else the other
+    design-matrix models opt in to raises before any device work."""
     if what is not None and model.glm is not None and model.glm.softmax:
         raise ValueError(f"{what}: softmax regression (Categorical(logits=X @ B)) runs under "
                          "hmc() / MCMC.run(method='hmc') on k_glm_softmax_grad without a mass "
                          "matrix; the column-split kernel (glm_kernel='wide'), NUTS "
-                         "(nuts_kernel='glm'), pointwise_log_likelihood / waic, "
-                         "posterior_predictive(predictive_kernel='glm') and "
-                         "loo(loo_kernel='glm') do not take it yet")
+                         "(nuts_kernel='glm'), posterior_predictive(predictive_kernel='glm') "
+                         "and loo(loo_kernel='glm') do not take it yet; "
+                         "pointwise_log_likelihood / waic take its likelihood alone when "
+                         "asked to (pointwise_kernel='glm')")
 
 
 _GLM_POINTWISE_FORM = (
@@ -2181,8 +2183,14 @@ def check_loo_kernel(loo_kernel: str) -> None:
         raise ValueError(f"loo_kernel must be 'auto' or 'glm', not {loo_kernel!r}")
 
 
+def check_pointwise_kernel(pointwise_kernel: str) -> None:
+    if pointwise_kernel not in ("auto", "glm"):
+        raise ValueError(f"pointwise_kernel must be 'auto' or 'glm', not {pointwise_kernel!r}")
+
+
 def pointwise_program(log_likelihood_fn, layout: ParamLayout,
-                      glm: Optional[str] = None, require_glm: Optional[str] = None) -> Program:
+                      glm: Optional[str] = None, require_glm: Optional[str] = None,
+                      softmax: bool = False) -> Program:
     """A likelihood traced like ``log_prob`` over the parameters of ``layout``,
     its terms in trace order (every element one observation), with the
     pointwise view enabled (diagnostics.pointwise_log_likelihood).  A
@@ -2192,17 +2200,22 @@ def pointwise_program(log_likelihood_fn, layout: ParamLayout,
     caller's name (LOO, predictive) for the ValueError that refuses it.
     require_glm: the caller's name where only a design-matrix likelihood runs
     (posterior_predictive(predictive_kernel="glm")), for the ValueError that
-    refuses any other."""
+    refuses any other.  softmax: the one caller that takes a softmax likelihood
+    (``Categorical(logits=X @ B [+ a])``, on csrc/glm_softmax_pointwise.h) —
+    pointwise_log_likelihood / waic under pointwise_kernel="glm"; every other
+    caller refuses it by name."""
     init = {n: np.zeros(shp, np.float32) for n, shp in zip(layout.names, layout.shapes)}
     model = trace(log_likelihood_fn, init, keep_order=True)
     if glm is not None:
         refuse_glm(model, glm)
-    refuse_softmax(model, require_glm or "the pointwise log-likelihood (waic, loo, predictive)")
+    if not softmax:
+        refuse_softmax(model, require_glm or "the pointwise log-likelihood (waic, loo, predictive)")
     if require_glm is not None and model.glm is None:
         raise ValueError(f"{require_glm} takes a design-matrix likelihood only: "
                          + _GLM_POINTWISE_FORM)
     if model.glm is not None and model.terms:
-        raise ValueError(f"{len(model.terms)} term(s) beside the X @ beta likelihood: "
+        raise ValueError((f"{require_glm}: " if softmax else "")
+                         + f"{len(model.terms)} term(s) beside the X @ beta likelihood: "
                          + _GLM_POINTWISE_FORM)
     _lib.require_device()
     prog = Program(model)

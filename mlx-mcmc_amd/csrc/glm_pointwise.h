@@ -54,6 +54,64 @@ MC_DEV void gpw_wave_sync() {
 
 MC_DEV double gpw_from_upper(double x) { return __shfl_down(x, 32); }
 
+// The turn's second half: the wave's patch pt holds the values of its 32 rows
+// under the 32 draws n0 .. n0 + 31 (row-major, leading dimension kGpwLd); the
+// lane is observation j (o of N; own: a live one) and takes draws 16 h ..
+// 16 h + 15, those before r1, as two batches of kPwBatch.
+MC_DEV void gpw_turn(PwAcc& A, double& nfsum, const float* pt, int j, int h, int64_t n0, int64_t r1,
+                     float* __restrict__ matrix, bool own, int64_t N, int64_t o) {
+#pragma unroll 1
+    for (int b = 0; b < 2; ++b) {
+        const int d0 = 16 * h + kPwBatch * b;
+        const int64_t left = r1 - (n0 + d0);
+        const int kb = left >= kPwBatch ? kPwBatch : (left > 0 ? (int)left : 0);
+        if (kb == 0) continue;
+        // the batch's kb values at the end of the window, in draw order
+        float x[kPwBatch];
+#pragma unroll
+        for (int k = 0; k < kPwBatch; ++k) {
+            const int d = d0 + k - (kPwBatch - kb);
+            x[k] = k >= kPwBatch - kb ? pt[j * kGpwLd + d] : 0.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < kPwBatch; ++k) {
+            if (k >= kPwBatch - kb) {
+                const int d = d0 + k - (kPwBatch - kb);
+                if (matrix && own) matrix[(n0 + d) * N + o] = x[k];
+                pw_lse(A, x[k]);
+            }
+        }
+        pw_moments(A, nfsum, x, kb);
+    }
+}
+
+// The upper half's draws join the lower half's, lower first; lane (observation,
+// h = 0) writes the partial of its draw block: out is the block's PW_MAX entry
+// of the observation.
+MC_DEV void gpw_finish(PwAcc& A, double nfsum, int h, bool own, double* __restrict__ out,
+                       int64_t N) {
+    if (A.nf > 0.0) {
+        A.mean = nfsum;
+        A.m2 = __builtin_nan("");
+    }
+    A.n = A.n + A.nf;
+    PwAcc U;
+    U.m = gpw_from_upper(A.m);
+    U.s = gpw_from_upper(A.s);
+    U.n = gpw_from_upper(A.n);
+    U.mean = gpw_from_upper(A.mean);
+    U.m2 = gpw_from_upper(A.m2);
+    U.nf = gpw_from_upper(A.nf);
+    if (h != 0 || !own) return;
+    if (U.n > 0.0) pw_merge(A, U);  // (a block of fewer than 17 draws: no upper half)
+    out[(int64_t)PW_MAX * N] = A.m;
+    out[(int64_t)PW_SUMEXP * N] = A.s;
+    out[(int64_t)PW_N * N] = A.n;
+    out[(int64_t)PW_MEAN * N] = A.mean;
+    out[(int64_t)PW_M2 * N] = A.m2;
+    out[(int64_t)PW_NONFINITE * N] = A.nf;
+}
+
 template <int FAM, int PT>
 __global__ void __launch_bounds__(256)
 k_glm_pointwise(GlmDev G, const float* __restrict__ norm, int64_t R, int64_t per,
@@ -167,57 +225,13 @@ k_glm_pointwise(GlmDev G, const float* __restrict__ norm, int64_t R, int64_t per
             }
         }
         gpw_wave_sync();
-        // turned: the lane is observation j and takes draws 16 h .. 16 h + 15
-#pragma unroll 1
-        for (int b = 0; b < 2; ++b) {
-            const int d0 = 16 * h + kPwBatch * b;
-            const int64_t left = r1 - (n0 + d0);
-            const int kb = left >= kPwBatch ? kPwBatch : (left > 0 ? (int)left : 0);
-            if (kb == 0) continue;
-            // the batch's kb values at the end of the window, in draw order
-            float x[kPwBatch];
-#pragma unroll
-            for (int k = 0; k < kPwBatch; ++k) {
-                const int d = d0 + k - (kPwBatch - kb);
-                x[k] = k >= kPwBatch - kb ? pt[j * kGpwLd + d] : 0.0f;
-            }
-#pragma unroll
-            for (int k = 0; k < kPwBatch; ++k) {
-                if (k >= kPwBatch - kb) {
-                    const int d = d0 + k - (kPwBatch - kb);
-                    if (matrix && own) matrix[(n0 + d) * (int64_t)G.N + o] = x[k];
-                    pw_lse(A, x[k]);
-                }
-            }
-            pw_moments(A, nfsum, x, kb);
-        }
+        gpw_turn(A, nfsum, pt, j, h, n0, r1, matrix, own, G.N, o);
         __syncthreads();  // every wave is done with coef / ex (and its patch)
         if (more) store();
         __syncthreads();
     }
 
-    // ---- the upper half's draws join the lower half's, lower first -----------
-    if (A.nf > 0.0) {
-        A.mean = nfsum;
-        A.m2 = __builtin_nan("");
-    }
-    A.n = A.n + A.nf;
-    PwAcc U;
-    U.m = gpw_from_upper(A.m);
-    U.s = gpw_from_upper(A.s);
-    U.n = gpw_from_upper(A.n);
-    U.mean = gpw_from_upper(A.mean);
-    U.m2 = gpw_from_upper(A.m2);
-    U.nf = gpw_from_upper(A.nf);
-    if (h != 0 || !own) return;
-    if (U.n > 0.0) pw_merge(A, U);  // (a block of fewer than 17 draws: no upper half)
-    double* out = part + (int64_t)blockIdx.y * PW_COUNT * G.N + o;
-    out[(int64_t)PW_MAX * G.N] = A.m;
-    out[(int64_t)PW_SUMEXP * G.N] = A.s;
-    out[(int64_t)PW_N * G.N] = A.n;
-    out[(int64_t)PW_MEAN * G.N] = A.mean;
-    out[(int64_t)PW_M2 * G.N] = A.m2;
-    out[(int64_t)PW_NONFINITE * G.N] = A.nf;
+    gpw_finish(A, nfsum, h, own, part + (int64_t)blockIdx.y * PW_COUNT * G.N + o, G.N);
 }
 
 }  // namespace mc

@@ -1,12 +1,16 @@
 // run_glm_pointwise.hip — the pointwise view of a design-matrix program and the
-// launches of csrc/glm_pointwise.h: what mc_program_num_elements,
+// launches of csrc/glm_pointwise.h (a softmax program: those of
+// csrc/glm_softmax_pointwise.h): what mc_program_num_elements,
 // mc_program_enable_pointwise, mc_pointwise_workspace_bytes and
 // mc_pointwise_stats (run_pointwise.hip) do on a program of
-// mc_program_create_glm.  The view lives in the GlmPlan, never in
-// mc_program::pw: the PSIS and predictive units, written against a PwCtx, see
-// no view on such a program and decline it by name.
+// mc_program_create_glm or mc_program_create_glm_softmax.  The view lives in the
+// GlmPlan, never in mc_program::pw: the PSIS and predictive units, written
+// against a PwCtx, see no view on such a program and decline it by name (and
+// mc_glm_psis_* / mc_glm_predictive* decline a softmax program by its plan,
+// enabled or not).
 #include "host.h"
 #include "glm_pointwise.h"
+#include "glm_softmax_pointwise.h"
 
 #include <cmath>
 
@@ -15,15 +19,12 @@ int64_t glm_pw_elements(const mc_program* p) { return p->glm->dev.N; }
 // The view: the per-observation normaliser -lgamma(y + 1) of the Poisson
 // family (what the sampler folds into lp_const as one sum), from the f32 y in
 // float64, rounded once to f32; 0 outside the support (the value is -inf
-// there) and for the other families.  X, X^T, y and the offset are the plan's.
+// there) and for the other families (a softmax program's kernel does not read
+// it: there the view only marks the program as enabled).  X, X^T, y and the
+// offset are the plan's.
 int glm_pw_enable(mc_program* p) {
     GlmPlan* g = p->glm;
     if (g->d_norm) return MC_OK;
-    if (g->softmax)
-        return fail(MC_ERR_UNSUPPORTED,
-                    "pointwise: a softmax program (mc_program_create_glm_softmax) has no pointwise "
-                    "view yet: k_glm_pointwise forms one linear predictor per draw, not K class "
-                    "logits");
     if (g->wide)
         return fail(MC_ERR_UNSUPPORTED,
                     "pointwise: a program of mc_program_create_glm_wide (glm_kernel=\"wide\") has no "
@@ -83,6 +84,24 @@ void launch_family(int PT, dim3 grid, hipStream_t st, const mc::GlmDev& G, const
     else go(mc::k_glm_pointwise<FAM, 8>);
 }
 
+template <int PT>
+int launch_softmax(int Kp, dim3 grid, hipStream_t st, const mc::GlmDev& G, int64_t R, int64_t per,
+                   const float* samples, double* part, float* matrix) {
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, G, R, per, samples, part, matrix);
+        return MC_OK;
+    };
+    switch (Kp) {
+        case 2: return go(mc::k_glm_softmax_pointwise<PT, 2>);
+        case 4: return go(mc::k_glm_softmax_pointwise<PT, 4>);
+        case 8: return go(mc::k_glm_softmax_pointwise<PT, 8>);
+        case 16: return go(mc::k_glm_softmax_pointwise<PT, 16>);
+        case 32: return go(mc::k_glm_softmax_pointwise<PT, 32>);
+        default: return fail(MC_ERR_INVALID, "k_glm_softmax_pointwise has no instantiation Kp = %d",
+                             Kp);
+    }
+}
+
 }  // namespace
 
 int glm_pw_stats(const mc_program* p, int64_t C, int64_t S, const float* samples, double* stats,
@@ -103,7 +122,16 @@ int glm_pw_stats(const mc_program* p, int64_t C, int64_t S, const float* samples
     // one block of draws: its partial is the result
     double* part = B > 1 ? (double*)ws : stats;
     const dim3 grid((unsigned)((g->dev.NT + 3) / 4), (unsigned)B);
-    if (g->dev.family == MC_GLM_NORMAL)
+    if (g->softmax) {
+        auto go = [&](auto launch) {
+            return launch(g->dev.Kp, grid, st, g->dev, R, per, samples, part, matrix);
+        };
+        const int rc = g->PT == 1   ? go(launch_softmax<1>)
+                       : g->PT == 2 ? go(launch_softmax<2>)
+                       : g->PT == 4 ? go(launch_softmax<4>)
+                                    : go(launch_softmax<8>);
+        if (rc != MC_OK) return rc;
+    } else if (g->dev.family == MC_GLM_NORMAL)
         launch_family<MC_GLM_NORMAL>(g->PT, grid, st, g->dev, g->d_norm, R, per, samples, part,
                                      matrix);
     else if (g->dev.family == MC_GLM_BERNOULLI_LOGIT)

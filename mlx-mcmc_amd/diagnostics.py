@@ -450,7 +450,7 @@ def _pointwise_launch(prog, x, matrix=False):
 
 
 def pointwise_log_likelihood(log_likelihood_fn, samples, layout=None, *, matrix=False,
-                             group=None):
+                             group=None, pointwise_kernel="auto"):
     """Per-observation log-likelihood statistics over the kept draws.
 
     ``log_likelihood_fn(params)`` is written and traced exactly like
@@ -477,15 +477,31 @@ def pointwise_log_likelihood(log_likelihood_fn, samples, layout=None, *, matrix=
     float32 device tensor of every value, when ``matrix=True`` (small problems
     only).  With an initialised process group (``group=False`` stays local)
     the ranks' partials are gathered and merged in rank order; the matrix
-    stays this rank's."""
+    stays this rank's.
+
+    ``pointwise_kernel="glm"`` takes a design-matrix likelihood only, passed
+    alone, and with it softmax regression —
+    ``mx.sum(Categorical(logits=X @ B [+ a]).log_prob(y))``, K <= 32 classes, at
+    most 256 columns: observation i under a draw is
+    ``log_softmax(X_i @ B + a)[y_i]``, the class logits of all draws one FP32
+    MFMA product with (draw, class) pairs as its columns
+    (csrc/glm_softmax_pointwise.h), the same statistics and ``matrix``.  The
+    Normal, Bernoulli and Poisson families run exactly as under ``"auto"``; any
+    other likelihood is a ``ValueError``.  The default ``"auto"`` keeps refusing
+    a softmax likelihood."""
     import torch
 
     from . import _trace
 
+    _trace.check_pointwise_kernel(pointwise_kernel)
     # (the likelihood is traced, and a form with no pointwise view refused, before
     # the device is asked for)
     draws, lay = _pointwise_host_inputs(samples, layout)
-    prog = _trace.pointwise_program(log_likelihood_fn, lay)
+    if pointwise_kernel == "glm":
+        prog = _trace.pointwise_program(log_likelihood_fn, lay,
+                                        require_glm="pointwise_kernel='glm'", softmax=True)
+    else:
+        prog = _trace.pointwise_program(log_likelihood_fn, lay)
     x, lay = _pointwise_inputs(draws, lay)
     part, mat = _pointwise_launch(prog, x, matrix)
     out = merge_pointwise(_gather_parts(part, group))
@@ -513,15 +529,19 @@ def waic_from_stats(stats) -> dict:
                 "n_nonfinite": int(np.sum(stats["nonfinite"]))}
 
 
-def waic(log_likelihood_fn, samples, layout=None, *, group=None) -> dict:
+def waic(log_likelihood_fn, samples, layout=None, *, group=None,
+         pointwise_kernel="auto") -> dict:
     """WAIC of a likelihood over the kept draws (``pointwise_log_likelihood``'s
     arguments): ``elpd_waic``, ``p_waic``, ``waic`` (= -2 elpd), ``se``
     (= sqrt(M var_i elpd_i)), ``lppd``, the ``pointwise`` terms, ``n_obs``,
     ``n_draws``, ``n_high_p_waic`` (observations with p_waic_i > 0.4, where
     WAIC is unreliable) and ``n_nonfinite`` (draws outside an observation's
-    support: reported, never raised)."""
+    support: reported, never raised).  ``pointwise_kernel="glm"``: a
+    design-matrix likelihood only, softmax regression included
+    (``pointwise_log_likelihood``)."""
     return waic_from_stats(pointwise_log_likelihood(log_likelihood_fn, samples, layout,
-                                                    group=group))
+                                                    group=group,
+                                                    pointwise_kernel=pointwise_kernel))
 
 
 # ------------------------------------------------------------ PSIS-LOO -----

@@ -156,18 +156,24 @@ class MCMC:
             return dev, self.info.layout
         return self.samples, getattr(self.info, "layout", None)
 
-    def pointwise_log_likelihood(self, log_likelihood_fn, matrix=False):
+    def pointwise_log_likelihood(self, log_likelihood_fn, matrix=False, pointwise_kernel="auto"):
         """Per-observation log-likelihood statistics of ``log_likelihood_fn``
         (traced like ``log_prob``) over the kept draws, on the device
-        (diagnostics.pointwise_log_likelihood)."""
+        (diagnostics.pointwise_log_likelihood).  ``pointwise_kernel="glm"``: a
+        design-matrix likelihood only, softmax regression
+        (``Categorical(logits=X @ B [+ a])``) included, on the MFMA kernels."""
         samples, layout = self._kept_draws()
         return _diag.pointwise_log_likelihood(log_likelihood_fn, samples, layout,
-                                              matrix=matrix, group=False)
+                                              matrix=matrix, group=False,
+                                              pointwise_kernel=pointwise_kernel)
 
-    def waic(self, log_likelihood_fn):
-        """WAIC of ``log_likelihood_fn`` over the kept draws (diagnostics.waic)."""
+    def waic(self, log_likelihood_fn, pointwise_kernel="auto"):
+        """WAIC of ``log_likelihood_fn`` over the kept draws (diagnostics.waic).
+        ``pointwise_kernel="glm"``: a design-matrix likelihood only, softmax
+        regression included."""
         samples, layout = self._kept_draws()
-        return _diag.waic(log_likelihood_fn, samples, layout, group=False)
+        return _diag.waic(log_likelihood_fn, samples, layout, group=False,
+                          pointwise_kernel=pointwise_kernel)
 
     def loo(self, log_likelihood_fn, r_eff=1.0, loo_kernel="auto"):
         """PSIS-LOO of ``log_likelihood_fn`` over the kept draws, with the
